@@ -12,9 +12,16 @@ log-likelihood) and the per-tile temper + reweight + resampling-index launch.
 particle-steps per step = N * 100 per tile.  Multi-GPU: one process per GPU,
 each rank owns its own tile(s) (weak scaling, no data-path collective); the
 timed region is bracketed by barrier + synchronize and the MAX over ranks is
-reported.  value = all ranks' particle-steps / that time.  The default run
-also times BASELINE configs[2] (C3: 64 tiles split over the ranks, strong
-scaling) with the same bracket and reports it as `c3_strong` (--no-c3 skips).
+reported.  value = all ranks' particle-steps / that time.
+
+A plain run does only that: set up, prewarm + warm up, the timed steps, the
+line (roofline objects from the step time), and --dump-outputs DIR if asked
+(the state the last timed step left, as .npy files).  --full adds everything
+else, each part with its own --no-* switch: the kernel-timing replay, the
+step-spread passes, BASELINE configs[2] (C3: 64 tiles split over the ranks,
+strong scaling, same bracket) as `c3_strong`, the C4 / C5 / C3-rank-share
+legs, a complete run(), the comparisons with the recorded reference runs and
+the CPU baseline.
 
 Roofline objects: `roofline` (HBM, as BASELINE.json asks): algorithmic bytes
 of the MH launch = 248 B per particle-step (state read+write
@@ -215,7 +222,54 @@ def parse():
     # GPU, no kernel): shard sizes, the barrier + MAX-over-ranks timing, the
     # rank-0-only line / vs_reference / cpu_baseline, the catalog gather
     ap.add_argument("--host-rehearsal", action="store_true")
-    return ap.parse_args()
+    # everything beyond the headline figure: the cold pass before the prewarm,
+    # the kernel-timing replay, the step-spread passes, the C3 / C4 / C5 legs,
+    # the complete run(), the comparisons with the recorded reference runs and
+    # the CPU baseline (each still has its own --no-* switch).  Without it the
+    # run sets up, warms up, times the --steps steps and prints the line.
+    ap.add_argument("--full", action="store_true")
+    # after the timed steps, write the sampler state their last step left (what
+    # a caller of the step receives) as DIR/<name>.npy (dump_outputs)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)
+    args = ap.parse_args()
+    if not args.full:
+        args.no_kernel_timing = args.no_spread = args.no_c3 = args.no_legs = True
+        args.no_full_run = args.no_vs_ref = args.no_cpu_baseline = True
+    return args
+
+
+DUMP_BUDGET = 64 * 2 ** 20  # --dump-outputs: bytes of array data in all
+SAMPLER_OUTPUTS = ("counts", "locs", "fluxes", "loglik", "weights_log_unnorm", "weights",
+                   "log_normalizing_constant", "temperature", "ess", "mutation_acc_rates")
+
+
+def dump_outputs(dirname, rank, arrays):
+    """--dump-outputs: each tensor as DIR/<name>.npy (rank r > 0:
+    <name>.rank<r>.npy), float64 kept, every other dtype as float32.  Outputs
+    over DUMP_BUDGET in all are cut to a fixed sample: the same seeded choice
+    of flat indices (sorted) for the same shapes, so two builds dump the same
+    elements."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy()
+        host[k] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64
+                                       else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    frac = min(1.0, 0.9 * DUMP_BUDGET / max(total, 1))
+    rng = np.random.default_rng(0)
+    for k, a in host.items():
+        if frac < 1.0 and a.size > 1024:
+            pick = np.sort(rng.choice(a.size, int(a.size * frac), replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(dirname, k + ("" if rank == 0 else f".rank{rank}") + ".npy"), a)
+
+
+def sampler_outputs(s):
+    """The state an SMC step hands its caller: the particles, their weights
+    and log-likelihoods, and the per-tile temperature / ESS / log Z."""
+    return {k: getattr(s, k) for k in SAMPLER_OUTPUTS if torch.is_tensor(getattr(s, k, None))}
 
 
 def mutation_kernel(args, K, full_recompute=False):
@@ -469,6 +523,9 @@ def bench_agg(args, dev, rank, world):
         return agg, time.perf_counter() - t0
     one(11 + 100 * rank)  # warm-up
     agg, elapsed = one(12 + 100 * rank)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {k: getattr(agg, k) for k in (
+            "counts", "locs", "fluxes", "weights", "log_evidence")})
     if world > 1:
         import torch.distributed as tdist
         on_dev = os.environ.get("SMCDET_DIST_BACKEND", "nccl") == "nccl"
@@ -533,6 +590,9 @@ def bench_mcmc(args, dev, rank, world):
     if world > 1:
         tdist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {k: getattr(s, k) for k in (
+            "counts", "locs", "fluxes", "accept")})
     if world > 1:
         on_dev = os.environ.get("SMCDET_DIST_BACKEND", "nccl") == "nccl"
         t = torch.tensor([elapsed], device=dev if on_dev else "cpu", dtype=torch.float64)
@@ -1026,19 +1086,20 @@ def main():
     prewarm = None
     cold = None
     if args.prewarm_s > 0 and not REHEARSAL:
-        # for the record: the same W + K steps timed from a cold chip first
-        # (what the line measured before round 5), then the prewarm
-        for _ in range(args.warmup):
-            step()
-        _sync()
-        t_c = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        _sync()
-        cold_ms = (time.perf_counter() - t_c) / args.steps * 1e3
-        cold = {"ms_per_step": cold_ms, "value": world * steps_per_step / (cold_ms * 1e-3),
-                "note": "the same W warmup + K timed steps before the prewarm (this rank; "
-                        "the chip's clock still ramping from idle)"}
+        # for the record (--full): the same W + K steps timed from a cold chip
+        # first (what the line measured before round 5), then the prewarm
+        if args.full:
+            for _ in range(args.warmup):
+                step()
+            _sync()
+            t_c = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            _sync()
+            cold_ms = (time.perf_counter() - t_c) / args.steps * 1e3
+            cold = {"ms_per_step": cold_ms, "value": world * steps_per_step / (cold_ms * 1e-3),
+                    "note": "the same W warmup + K timed steps before the prewarm (this rank; "
+                            "the chip's clock still ramping from idle)"}
         # the clock's ramp from idle, outside the measured run: untimed steps
         # until prewarm_s seconds have passed, then a fresh start of the same
         # sampler (initialise, first temper), so the timed steps are SMC
@@ -1069,6 +1130,8 @@ def main():
     if dist:
         tdist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, sampler_outputs(s))
     end_state = [x.detach().clone() for x in (s.log_normalizing_constant, s.temperature,
                                               s.locs)] if not REHEARSAL else None
     # The roofline's kernel durations describe the TIMED steps themselves: the
@@ -1252,7 +1315,7 @@ def main():
                 r = {"error": repr(e)}
             if r is not None:
                 out["smc"][key] = r
-    if REHEARSAL and rank == 0 and world == 1:
+    if REHEARSAL and args.full and rank == 0 and world == 1:
         out["cpu_baseline"] = {"rehearsal": f"cpu_baseline on rank {rank}"}
     if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "c2":
         try:

@@ -14,7 +14,7 @@ if [ -n "$TESTS" ]; then
     > $D/tests.log 2>&1
   rc=$?; tail -3 $D/tests.log; echo "tests rc=$rc"; [ $rc -ne 0 ] && exit $rc
 fi
-Q="--no-cpu-baseline --no-full-run --no-vs-ref --no-spread --no-c3"
+Q="--full --no-cpu-baseline --no-full-run --no-vs-ref --no-spread --no-c3"
 for rep in 1 2 3; do
   for v in bins indices; do
     extra=""; [ $v = indices ] && extra="--ancestor-indices"

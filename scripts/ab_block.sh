@@ -8,7 +8,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 D=gpurun_out/ab_block${TAG:-}
 mkdir -p $D
-Q="--steps 20 --warmup 5 --no-cpu-baseline --no-vs-ref --no-full-run --no-spread"
+Q="--full --steps 20 --warmup 5 --no-cpu-baseline --no-vs-ref --no-full-run --no-spread"
 [ "${LEGS:-0}" = "1" ] || Q="$Q --no-c3 --no-legs"
 for r in $(seq 1 ${REPS:-3}); do
   for fl in 0 16384; do

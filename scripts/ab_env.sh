@@ -11,7 +11,7 @@ for r in $(seq 1 $ROUNDS); do
     for v in 0 1; do
       out=gpurun_out/abenv/${wl}_${v}_r$r.json
       env ${ENVVAR}=$v timeout -k 10 240 python bench.py --workload $wl --no-cpu-baseline \
-        --no-full-run ${BENCH_ARGS:-} > $out.log 2>&1
+        --full --no-full-run ${BENCH_ARGS:-} > $out.log 2>&1
       rc=$?
       if [ $rc -ne 0 ]; then echo "$wl $v rc=$rc"; tail -5 $out.log; exit $rc; fi
       tail -1 $out.log > $out

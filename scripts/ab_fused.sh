@@ -11,6 +11,7 @@ if [ "${RUN_TESTS:-1}" = "1" ]; then
   rc=$?; echo "pytest rc=$rc"; grep -E "^FAILED|passed|failed" gpurun_out/pytest_gpu.log | tail -15
   if [ $rc -gt 1 ]; then exit $rc; fi
 fi
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # (roofline.kernel_ms below comes from the kernel-timing replay)
 for i in $(seq 1 ${ROUNDS:-2}); do
   timeout -k 10 200 python bench.py --no-cpu-baseline --no-full-run --fused-step ${BENCH_ARGS:-} > gpurun_out/b_fused_$i.log 2>&1 || exit $?
   timeout -k 10 200 python bench.py --no-cpu-baseline --no-full-run ${BENCH_ARGS:-} > gpurun_out/b_split_$i.log 2>&1 || exit $?

@@ -5,7 +5,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 D=gpurun_out/ab_prewarm
 mkdir -p $D
-Q="--steps 20 --warmup 5 --no-cpu-baseline --no-vs-ref --no-full-run --no-c3 --no-legs"
+Q="--full --steps 20 --warmup 5 --no-cpu-baseline --no-vs-ref --no-full-run --no-c3 --no-legs"
 for r in $(seq 1 ${REPS:-3}); do
   for pw in 0 2; do
     timeout -k 10 200 python bench.py $Q --prewarm-s $pw > $D/pw${pw}_r$r.log 2>&1 || exit $?

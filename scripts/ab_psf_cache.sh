@@ -11,7 +11,7 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_psf_cache.py tests/test_gpu
   > gpurun_out/ab_pc/pytest.log 2>&1
 rc=$?; echo "pytest rc=$rc"; grep -E "^FAILED|passed|failed" gpurun_out/ab_pc/pytest.log | tail -6
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-Q="--no-cpu-baseline --no-full-run --no-vs-ref --no-spread"
+Q="--full --no-cpu-baseline --no-full-run --no-vs-ref --no-spread"
 for rep in 1 2; do
   for wl in c4 c5; do
     for fl in 0 ${AB_FLAG:-2048}; do

@@ -14,7 +14,7 @@ timeout -k 10 500 python -u -m pytest ${TESTS:-tests/test_gpu_psf_cache.py tests
   --timeout-method thread > $D/pytest.log 2>&1
 rc=$?; echo "pytest rc=$rc"; grep -E "^FAILED|passed|failed" $D/pytest.log | tail -8
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-Q="--no-cpu-baseline --no-full-run --no-vs-ref --no-spread --no-c3"
+Q="--full --no-cpu-baseline --no-full-run --no-vs-ref --no-spread --no-c3"
 for rep in ${REPS:-1 2 3}; do
   for fl in 0 8192; do
     for wl in ${WLS:-c2 c4}; do

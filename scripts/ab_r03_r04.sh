@@ -8,7 +8,7 @@ D=gpurun_out/r03r04; mkdir -p $D
 Q0="--no-cpu-baseline --no-full-run --no-vs-ref --no-spread"
 for r in $(seq 1 ${ROUNDS:-3}); do
   for tree in r04 r03; do
-    dir=.; Q="$Q0 --no-c3"
+    dir=.; Q="--full $Q0 --no-c3"  # (the older trees' bench has no --full: all of it is their default)
     [ $tree = r03 ] && { dir=_r03; Q="$Q0"; }  # (round 3's bench had no --no-c3)
     for wl in "c2" "c4" "c2 --total-tiles 64"; do
       tag=$(echo "$wl" | tr ' ' '_' | tr -d '-')

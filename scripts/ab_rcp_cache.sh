@@ -12,7 +12,7 @@ timeout -k 10 500 python -u -m pytest tests/test_gpu_psf_cache.py tests/test_gpu
   --timeout-method thread > gpurun_out/ab_rv/pytest.log 2>&1
 rc=$?; echo "pytest rc=$rc"; grep -E "^FAILED|passed|failed" gpurun_out/ab_rv/pytest.log | tail -6
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-Q="--no-cpu-baseline --no-full-run --no-vs-ref --no-spread --no-c3"
+Q="--full --no-cpu-baseline --no-full-run --no-vs-ref --no-spread --no-c3"
 for rep in 1 2 3; do
   for fl in 0 4096; do
     for wl in c2 c3; do

@@ -19,7 +19,7 @@ for k in ("step2", "step3", "step4"):
     print(k, {a: round(b) for a, b in d[k]["tile_cycles"].items()})
 PY
 done
-Q="--no-cpu-baseline --no-full-run --no-vs-ref --no-spread --no-c3"
+Q="--full --no-cpu-baseline --no-full-run --no-vs-ref --no-spread --no-c3"
 for rep in 1 2 3; do
   for nt in 512 256; do
     SMCDET_TILE_THREADS=$nt timeout -k 10 200 python bench.py $Q > $D/c2_nt${nt}_r$rep.json 2> $D/c2_nt${nt}_r$rep.err

@@ -2,7 +2,7 @@ set -u
 cd "${GRAFT_REPO_ROOT}"
 export TMPDIR=/tmp
 D=gpurun_out/abt; mkdir -p $D
-Q="--no-cpu-baseline --no-full-run --no-vs-ref --no-spread --no-c3 --steps 20"
+Q="--full --no-cpu-baseline --no-full-run --no-vs-ref --no-spread --no-c3 --steps 20"
 for r in 1 2; do
 for tag in cur old; do
   lib=smcdet_amd/libsmcdet_hip.so; [ $tag = old ] && lib=smcdet_amd/libsmcdet_hip_old.so

@@ -9,7 +9,7 @@ O=gpurun_out/lines
 mkdir -p $O
 run() {  # $1 = name, rest = bench args
   local name=$1; shift
-  timeout -k 10 300 python bench.py "$@" > $O/$name.log 2>&1
+  timeout -k 10 300 python bench.py --full "$@" > $O/$name.log 2>&1
   local rc=$?
   echo "$name rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 $O/$name.log; exit $rc; fi
@@ -24,5 +24,5 @@ run mcmc --workload mcmc
 run mala --kernel mala --no-cpu-baseline
 run agg --workload agg --no-cpu-baseline
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_c4 -o run -- \
-  python3 bench.py --workload c4 --no-cpu-baseline --no-full-run > $O/prof_c4.log 2>&1
+  python3 bench.py --full --workload c4 --no-cpu-baseline --no-full-run > $O/prof_c4.log 2>&1
 echo "prof_c4 rc=$?"

@@ -18,6 +18,7 @@ timeout -k 10 300 python __graft_entry__.py smoke > gpurun_out/smoke.log 2>&1
 ok_or_stop $? smoke
 tail -3 gpurun_out/smoke.log
 if [ "${RUN_BENCH:-1}" = "1" ]; then
+  BENCH_ARGS="--full ${BENCH_ARGS:---steps 10 --warmup 2}"
   timeout -k 10 400 python bench.py ${BENCH_ARGS:---steps 10 --warmup 2} > gpurun_out/bench.log 2>&1
   ok_or_stop $? bench
   tail -2 gpurun_out/bench.log

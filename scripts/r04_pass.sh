@@ -24,7 +24,7 @@ if has tests; then
   grep -E "^FAILED|passed|failed" $D/pytest.log | tail -12
 fi
 if has bench; then
-  timeout -k 10 400 python bench.py > $D/bench.log 2>&1
+  timeout -k 10 400 python bench.py --full > $D/bench.log 2>&1
   step bench $?
   tail -c 700 $D/bench.log; echo
 fi
@@ -47,7 +47,7 @@ if has postbench; then
   # the bench line with this pass's counters: the PMC summary (same library
   # source hash) goes where bench.py reads it, then the default bench runs
   cp $D/pmc_mh_r04.json profiles/pmc_mh_r04.json
-  timeout -k 10 400 python bench.py > $D/bench_post.log 2>&1
+  timeout -k 10 400 python bench.py --full > $D/bench_post.log 2>&1
   step postbench $?
   tail -c 400 $D/bench_post.log; echo
 fi

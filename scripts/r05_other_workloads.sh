@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 D=gpurun_out/other_wl
 mkdir -p $D
-Q="--no-cpu-baseline --no-full-run --no-vs-ref --no-legs --no-c3 --no-spread"
+Q="--full --no-cpu-baseline --no-full-run --no-vs-ref --no-legs --no-c3 --no-spread"
 timeout -k 10 300 python bench.py --kernel mala $Q > $D/mala.log 2>&1 || exit $?
 timeout -k 10 300 python bench.py --workload mcmc $Q > $D/mcmc.log 2>&1 || exit $?
 timeout -k 10 300 python bench.py --workload agg $Q > $D/agg.log 2>&1 || exit $?

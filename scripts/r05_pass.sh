@@ -29,7 +29,7 @@ if has smoke; then
   tail -2 $D/smoke.log
 fi
 if has bench; then
-  timeout -k 10 400 python bench.py > $D/bench.log 2>&1
+  timeout -k 10 400 python bench.py --full > $D/bench.log 2>&1
   step bench $?
   tail -c 700 $D/bench.log; echo
 fi
@@ -64,7 +64,7 @@ if has postbench; then
   for f in pmc_mh_r05.json pmc_mh_c4_r05.json pmc_mh_c5_r05.json; do
     [ -f $D/$f ] && cp $D/$f profiles/$f
   done
-  timeout -k 10 400 python bench.py > $D/bench_post.log 2>&1
+  timeout -k 10 400 python bench.py --full > $D/bench_post.log 2>&1
   step postbench $?
   tail -c 400 $D/bench_post.log; echo
 fi

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 D=gpurun_out/r05_timing${TAG:-}
 mkdir -p $D
-Q="--no-cpu-baseline --no-vs-ref --no-full-run"
+Q="--full --no-cpu-baseline --no-vs-ref --no-full-run"
 for r in 1 2 3; do
   timeout -k 10 300 python bench.py --steps 20 --warmup 5 $Q > $D/bench_rep$r.log 2>&1 || exit $?
   python3 -c "import json,sys; d=json.loads(open('$D/bench_rep$r.log').read().strip().splitlines()[-1]); print('rep $r', d['ms_per_step'], d['value'], d['roofline']['kernel_ms'], d['step_spread']['repeat_passes_ms_per_step'], d.get('prewarm',{}) and d['prewarm']['steps'])"

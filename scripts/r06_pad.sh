@@ -34,7 +34,7 @@ if has pmc; then
     SMCDET_ALLOW_STALE=1 SMCDET_HIP_LIB=$PWD/$lib timeout -k 10 240 rocprofv3 \
       --pmc SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_INST_ANY \
       --kernel-include-regex mh_sweep -T -f csv -d $D/pmc_$tag -o run -- \
-      python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-full-run --no-vs-ref --no-c3 \
+      python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-full-run --no-vs-ref --no-c3 \
       --no-legs --no-spread --prewarm-s 0 > $D/pmc_$tag.log 2>&1
     step pmc_$tag $?
   done

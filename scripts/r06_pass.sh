@@ -53,7 +53,7 @@ if has paired; then
   tail -4 $D/paired_all.log
 fi
 if has bench; then
-  timeout -k 10 400 python bench.py > $D/bench.log 2>&1
+  timeout -k 10 400 python bench.py --full > $D/bench.log 2>&1
   step bench $?
   tail -c 700 $D/bench.log; echo
 fi
@@ -71,7 +71,7 @@ if has trace; then
   # tile durations the line reports as step_attribution -- the two must agree
   mkdir -p $D/trace_bench
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -T -f csv -d $D/trace_bench -o run -- \
-    python3 bench.py --no-c3 --no-legs --no-vs-ref --no-full-run --no-cpu-baseline --no-spread \
+    python3 bench.py --full --no-c3 --no-legs --no-vs-ref --no-full-run --no-cpu-baseline --no-spread \
     > $D/trace_bench.log 2>&1
   step trace $?
   tr=$(find $D/trace_bench -name 'run_kernel_trace.csv' | head -1)
@@ -101,7 +101,7 @@ if has postbench; then
   for f in pmc_mh_r06.json pmc_mh_c4_r06.json pmc_mh_c5_r06.json; do
     [ -f $D/$f ] && cp $D/$f profiles/$f
   done
-  timeout -k 10 400 python bench.py > $D/bench_post.log 2>&1
+  timeout -k 10 400 python bench.py --full > $D/bench_post.log 2>&1
   step postbench $?
   tail -c 400 $D/bench_post.log; echo
 fi

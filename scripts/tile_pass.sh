@@ -31,7 +31,7 @@ timeout -k 10 200 python scripts/host_profile.py > $D/host_profile.txt 2>&1
 rc=$?; head -30 $D/host_profile.txt; [ $rc -ne 0 ] && { echo "host_profile rc=$rc"; exit $rc; }
 timeout -k 10 200 python scripts/startup_probe.py > $D/startup.log 2>&1
 rc=$?; tail -1 $D/startup.log | cut -c1-600; [ $rc -ne 0 ] && { echo "startup rc=$rc"; exit $rc; }
-Q="--no-cpu-baseline --no-full-run --no-vs-ref --no-spread --no-c3"
+Q="--full --no-cpu-baseline --no-full-run --no-vs-ref --no-spread --no-c3"
 for nt in 512 256; do
   SMCDET_TILE_THREADS=$nt timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -f csv -d $D/trace_$nt -o run -- \
     python3 bench.py $Q --steps 20 > $D/trace_$nt.log 2>&1

@@ -27,16 +27,74 @@ def test_c3_split_partitions_tiles_like_the_library(world):
     assert seen == list(range(total))
 
 
-def test_c3_leg_is_part_of_the_default_run():
+def _parse(argv):
     old = sys.argv
     try:
-        sys.argv = ["bench.py"]
-        args = bench.parse()
+        sys.argv = ["bench.py"] + argv
+        return bench.parse()
     finally:
         sys.argv = old
-    # the leg runs for the default C2 command (c3_leg's guard in main)
+
+
+def test_c3_leg_is_part_of_the_default_run():
+    args = _parse(["--full"])
+    # the leg runs for the default C2 command with --full (c3_leg's guard in main)
     assert (args.workload, args.kernel, args.total_tiles, args.tiles_per_gpu,
             args.no_c3) == ("c2", "mh", 0, 1, False)
+
+
+def test_plain_run_does_only_the_timed_steps():
+    """Without --full every extra of the line is off (the kernel-timing replay,
+    the spread passes, the legs, the complete run, the reference comparisons,
+    the CPU baseline); with it each is on unless its own --no-* switch says so."""
+    extras = ("no_kernel_timing", "no_spread", "no_c3", "no_legs", "no_full_run", "no_vs_ref",
+              "no_cpu_baseline")
+    plain, full = _parse([]), _parse(["--full", "--no-spread"])
+    assert not plain.full and all(getattr(plain, k) for k in extras)
+    assert full.full and [k for k in extras if getattr(full, k)] == ["no_spread"]
+
+
+def test_dump_outputs_writes_the_last_steps_state(tmp_path):
+    """--dump-outputs DIR (host rehearsal, one rank): the sampler's state after
+    the timed steps as float32 .npy files, the same from run to run."""
+    import json
+    import subprocess
+
+    import numpy as np
+
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                            "--host-rehearsal", "--particles", "64", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(d)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert line["steps"] == 3 and line["ms_per_step"] >= 0.95
+        assert "c3_strong" not in line and "cpu_baseline" not in line
+        return {p.name: np.load(p) for p in sorted(d.iterdir())}
+
+    a, b = run(tmp_path / "a"), run(tmp_path / "b")
+    assert {"counts.npy", "locs.npy", "fluxes.npy", "weights.npy", "temperature.npy", "ess.npy",
+            "log_normalizing_constant.npy"} <= set(a)
+    assert a["locs.npy"].shape == (1, 1, 64, 10, 2)
+    for k in a:
+        assert a[k].dtype == np.float32
+        assert np.array_equal(a[k], b[k])
+
+
+def test_dump_outputs_samples_large_outputs_within_the_budget(tmp_path):
+    import numpy as np
+    import torch
+    big = torch.arange(12 * 2 ** 20, dtype=torch.float32)  # 48 MiB + 32 MiB > the budget
+    arrays = {"big": big, "big64": big.double()[:4 * 2 ** 20], "small": torch.ones(3, 5)}
+    bench.dump_outputs(str(tmp_path / "a"), 0, arrays)
+    bench.dump_outputs(str(tmp_path / "b"), 1, arrays)
+    a = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= bench.DUMP_BUDGET
+    assert a["big64.npy"].dtype == np.float64 and a["small.npy"].shape == (3, 5)
+    # a sorted sample without repeats, the same one on every call
+    assert np.all(np.diff(a["big.npy"]) > 0) and a["big.npy"].size > 6 * 2 ** 20
+    assert np.array_equal(a["big.npy"], np.load(tmp_path / "b" / "big.rank1.npy"))
 
 
 def _torchrun_rehearsal(extra, world=2):
@@ -51,7 +109,7 @@ def _torchrun_rehearsal(extra, world=2):
     env = dict(os.environ, SMCDET_DIST_BACKEND="gloo", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            f"--nproc-per-node={world}", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--host-rehearsal",
+           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--host-rehearsal", "--full",
            "--particles", "64", "--steps", "4", "--warmup", "1"] + extra
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
