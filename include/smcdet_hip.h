@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMCDET_ABI_VERSION 18
+#define SMCDET_ABI_VERSION 19
 
 /* status codes */
 #define SMCDET_OK 0
@@ -490,6 +490,50 @@ int smcdet_prune(const float* locs, const float* fluxes, int32_t T, int32_t N,
                  int32_t S, float tile_dim, float flux_threshold,
                  int64_t* counts_out, float* locs_out, float* fluxes_out,
                  void* stream);
+
+/* ---- evaluation (smcdet/metrics.py:8-84, match_catalogs) ----------------- */
+#define SMCDET_MATCH_MAX_SOURCES 64 /* St, Se: one source per lane */
+#define SMCDET_MATCH_MAX_BINS 64    /* B: one magnitude bin per lane */
+
+/* Matches sampled catalogs to a true catalog, tile by tile, and counts sources
+ * and matches per magnitude bin.  Layouts are smcdet_prune's, kept sources
+ * first:
+ *   true_counts [T] int32, true_locs [T,St,2], true_fluxes [T,St]
+ *   est_counts [T,N] int32, est_locs [T,N,Se,2], est_fluxes [T,N,Se]
+ * (the counts are int32: cast smcdet_prune's int64 or the samplers' float32).
+ * index [T,M] int64 (nullable), values in [0, N): catalog index[t,j] of tile t
+ * is problem (t, j).  Null: M must equal N and problem (t, j) is catalog j.
+ * Per problem, with n / m the two counts clamped to [0,St] / [0,Se] (only the
+ * first n / m slots are read; padding may hold anything):
+ *   mag = 22.5 - 2.5 log10(flux); a pair is in tolerance iff its Euclidean
+ *   distance <= locs_tol and |delta mag| <= mags_tol (the reference's strict
+ *   `>` for out of bounds, metrics.py:51-57).  The matching is the exact
+ *   lexicographic optimum: the largest number of in-tolerance pairs, then the
+ *   smallest sum of their distances (what the reference's cost
+ *   locs_dist + oob * 1e20 intends; its float32 / float64 sums swallow the
+ *   distances whenever an out-of-tolerance pair must be assigned).  Ties of
+ *   the objective: one optimum, the same on every run.
+ *   A source with a non-finite location or a non-finite or non-positive flux
+ *   is out of tolerance with everything (the reference raises from scipy).
+ * Outputs, each [T,M,B] float32 (metrics.py:67-77): a source of magnitude x
+ * is counted in bin b = torch.bucketize(x, mag_bins), mag_bins[b-1] < x <=
+ * mag_bins[b] (mag_bins [B] ascending; b = 0 is everything <= mag_bins[0];
+ * b = B, fainter than the last edge, and a NaN magnitude are counted nowhere).
+ * true_total / est_total bin all n / m sources, true_matches / est_matches
+ * the matched ones.  match_of_true [T,M,St] int32 (nullable): the est slot
+ * matched to true source i, or -1 (also for i >= n).
+ * St, Se <= SMCDET_MATCH_MAX_SOURCES and B <= SMCDET_MATCH_MAX_BINS, else
+ * SMCDET_EUNSUPPORTED before any device work; null required buffers, T, N or
+ * M < 1, a non-positive tolerance, or a null index with M != N: SMCDET_EINVAL. */
+int smcdet_match_catalogs(const int32_t* true_counts, const float* true_locs,
+                          const float* true_fluxes, const int32_t* est_counts,
+                          const float* est_locs, const float* est_fluxes,
+                          const int64_t* index, int32_t T, int32_t N, int32_t M,
+                          int32_t St, int32_t Se, float locs_tol, float mags_tol,
+                          const float* mag_bins, int32_t B, float* true_total,
+                          float* true_matches, float* est_total,
+                          float* est_matches, int32_t* match_of_true,
+                          void* stream);
 
 /* ---- tile aggregation (smcdet/aggregate.py:8-593, Aggregate) ------------- */
 #define SMCDET_AGG_MAX_SOURCES 4096

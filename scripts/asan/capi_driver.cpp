@@ -126,6 +126,23 @@ int main() {
                                 nullptr, nullptr, nullptr, nullptr), SMCDET_EINVAL);
   EXPECT(smcdet_gather(idx, 1, 4, 2, d, d, d, d, d, d, nullptr), SMCDET_EINVAL);
   EXPECT(smcdet_prune(nullptr, d, 1, 1, 1, 8.f, 0.25f, idx, d, d, nullptr), SMCDET_EINVAL);
+  // catalog matching: null buffers, sizes, tolerances, null index with M != N, limits
+  EXPECT(smcdet_match_catalogs(nullptr, d, d, ws, d, d, nullptr, 1, 1, 1, 4, 4, 0.5f, 0.5f, d, 4, d,
+                               d, d, d, nullptr, nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_match_catalogs(ws, d, d, ws, d, d, nullptr, 1, 1, 1, 4, 4, 0.5f, 0.5f, d, 4, d, d,
+                               d, nullptr, nullptr, nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_match_catalogs(ws, d, d, ws, d, d, nullptr, 0, 1, 1, 4, 4, 0.5f, 0.5f, d, 4, d, d,
+                               d, d, nullptr, nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_match_catalogs(ws, d, d, ws, d, d, nullptr, 1, 1, 1, 4, 4, 0.f, 0.5f, d, 4, d, d,
+                               d, d, nullptr, nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_match_catalogs(ws, d, d, ws, d, d, nullptr, 1, 4, 2, 4, 4, 0.5f, 0.5f, d, 4, d, d,
+                               d, d, nullptr, nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_match_catalogs(ws, d, d, ws, d, d, nullptr, 1, 1, 1, 65, 4, 0.5f, 0.5f, d, 4, d,
+                               d, d, d, nullptr, nullptr), SMCDET_EUNSUPPORTED);
+  EXPECT(smcdet_match_catalogs(ws, d, d, ws, d, d, nullptr, 1, 1, 1, 4, 65, 0.5f, 0.5f, d, 4, d,
+                               d, d, d, nullptr, nullptr), SMCDET_EUNSUPPORTED);
+  EXPECT(smcdet_match_catalogs(ws, d, d, ws, d, d, nullptr, 1, 1, 1, 4, 4, 0.5f, 0.5f, d, 65, d,
+                               d, d, d, nullptr, nullptr), SMCDET_EUNSUPPORTED);
   EXPECT(smcdet_count_posterior(d, d, 0, 1, 100000, 4, 1, 4, SMCDET_RESAMPLE_SYSTEMATIC, 0, 0,
                                 nullptr, nullptr, d, d, d, d, idx, d, d, d, nullptr),
          SMCDET_EUNSUPPORTED);

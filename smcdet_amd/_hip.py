@@ -25,7 +25,7 @@ SMCDET_RESAMPLE_SYSTEMATIC = 1
 SMCDET_MH_FULL_RECOMPUTE = 1
 SMCDET_MH_COMPONENT_BY_COUNT = 2
 SMCDET_MH_SKIP_DONE = 4
-ABI_VERSION = 18
+ABI_VERSION = 19
 SMCDET_SMC_FREEZE_DONE = 1
 SMCDET_SMC_TWO_LAUNCH = 2
 
@@ -40,6 +40,8 @@ MAX_PARTICLES = 16384       # N per tile: the tile kernel holds 32 log-likelihoo
 MAX_TILES = 65535           # T: the MH grid's y dimension
 MAX_PSF_RADIUS = 64
 MAX_AGG_SOURCES = 4096      # sources of an aggregated (joint) tile (LDS or workspace catalog)
+MATCH_MAX_SOURCES = 64      # SMCDET_MATCH_MAX_SOURCES: sources per catalog in match_catalogs
+MATCH_MAX_BINS = 64         # SMCDET_MATCH_MAX_BINS: magnitude bins in match_catalogs
 
 
 def check_limits(H, W, S, N=None, T=None, R=None, where="sampler", global_ok=False):
@@ -151,6 +153,8 @@ _SIGS = {
     "smcdet_count_posterior": ([c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_u64, c_u64, c_p,
                                 c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
     "smcdet_prune": ([c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p], c_i),
+    "smcdet_match_catalogs": ([c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f,
+                               c_f, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
     "smcdet_aggregate_sweep": ([c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p,
                                 c_p, c_p, c_p, c_u64, c_u64, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                 c_p], c_i),
@@ -190,6 +194,7 @@ _OUTS = {
     "smcdet_bins_index": ((3,), ()),
     "smcdet_count_posterior": ((16, 17, 18, 19, 20), ()),
     "smcdet_prune": ((7, 8, 9), ()),
+    "smcdet_match_catalogs": ((16, 17, 18, 19, 20), ()),
     "smcdet_aggregate_sweep": ((13, 14, 15, 19, 20, 21, 22, 24), ((10, 13), (11, 14), (12, 15))),
     "smcdet_aggregate_temper": ((10,), ()),
     "smcdet_aggregate_reweight": ((10, 11, 12, 13, 17), ()),
@@ -287,7 +292,8 @@ SOURCES = tuple(os.path.join(_REPO, p) for p in (
     "smcdet_amd/csrc/common.hip", "smcdet_amd/csrc/model_kernels.hip",
     "smcdet_amd/csrc/mh_kernel.hip", "smcdet_amd/csrc/mala_kernel.hip",
     "smcdet_amd/csrc/chain_kernel.hip", "smcdet_amd/csrc/smc_kernels.hip",
-    "smcdet_amd/csrc/agg_kernel.hip", "smcdet_amd/csrc/device.h", "smcdet_amd/csrc/render.h",
+    "smcdet_amd/csrc/agg_kernel.hip", "smcdet_amd/csrc/match_kernel.hip",
+    "smcdet_amd/csrc/device.h", "smcdet_amd/csrc/render.h",
     "smcdet_amd/csrc/mcmc.h", "smcdet_amd/csrc/tile.h", "include/smcdet_hip.h"))
 
 
