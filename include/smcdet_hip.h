@@ -217,7 +217,12 @@ int smcdet_psf_dense(const smcdet_image_model_t* model, const float* locs,
                      int32_t T, int32_t N, int32_t S, float* psf, void* stream);
 
 /* Noise draw for ImageModel.sample (images.py:78-83 Poisson, :147-157
- * Normal): image[T,H,W,N] from rate[T,H,W,N] (in place allowed). */
+ * Normal): image[T,H,W,N] from rate[T,H,W,N] (in place allowed).  Element i
+ * draws from the Philox counter offset + i, so a call at offset k repeats
+ * elements k.. of the call at offset 0.  Poisson draws follow the Poisson law
+ * for rates up to 1e6 (the supported ceiling: the transformed-rejection
+ * candidate is float32, its acceptance test double); a rate that is zero,
+ * negative or NaN gives 0. */
 int smcdet_sample_image(const smcdet_image_model_t* model, const float* rate,
                         int64_t count, uint64_t seed, uint64_t offset,
                         float* image, void* stream);
@@ -273,7 +278,10 @@ int smcdet_prior_sample(const smcdet_prior_t* prior, int32_t T,
  * go (nullable, int32 device scalar): when *go == 0 the launch does nothing
  * (no output is written) -- lets a host enqueue the next SMC iteration before
  * it has read the loop condition (see smcdet_temper_reweight's `live`).
- * tile_boxes (nullable): per-tile location boxes in place of mh->locs_min/max. */
+ * tile_boxes (nullable): per-tile location boxes in place of mh->locs_min/max.
+ * Tiles wider than 256 pixels: without SMCDET_MH_FULL_RECOMPUTE,
+ * 2*psf_radius + 2 + 4.8*locs_stdev must not exceed 256 (the widest window
+ * that an old and a proposed position can span), else SMCDET_EUNSUPPORTED. */
 int smcdet_mh_sweep(const smcdet_image_model_t* model,
                     const smcdet_prior_t* prior, const smcdet_mh_t* mh,
                     const float* tiled_image, const float* temperature,

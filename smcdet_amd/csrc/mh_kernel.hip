@@ -828,7 +828,10 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
 #ifdef SMCDET_TRACE
       tr_pos += npos;
 #endif
-      const unsigned magic = (unsigned)readlane((int)bmg, b3 + 1);  // q/bw, q < 1024
+      // q / bw for the register slots' q < 384 (kSlots * 64): exact for bw <= 256,
+      // checked exhaustively on the host; wider union windows are refused by
+      // the entry point (mh_sweep_impl's check of W, psf_radius and locs_stdev)
+      const unsigned magic = (unsigned)readlane((int)bmg, b3 + 1);
       const bool same = (fh0 == fh1) && (fw0 == fw1);
       const int ao_h = fh0 - m.R - r0, ao_w = fw0 - m.R - c0;
       const int an_h = fh1 - m.R - r0, an_w = fw1 - m.R - c0;
@@ -1580,6 +1583,17 @@ static int mh_sweep_impl(const smcdet_image_model_t* model, const smcdet_prior_t
     return set_error(SMCDET_EINVAL, "incomplete replay buffers");
   if (!(mh->locs_stdev > 0.f) || !(mh->fluxes_stdev > 0.f))
     return set_error(SMCDET_EINVAL, "proposal standard deviations must be > 0");
+  // The sweep splits a union-window position q < 384 into row and column with a
+  // 16-bit reciprocal of the window's width bw, exact for bw <= 256 (bw = 257
+  // puts q = 256 in row 1).  bw <= min(W, 2R + 2 + jump), and a proposal lands
+  // within 4.76 locs_stdev of a current value inside the box (its uniform is
+  // clamped to [1e-6, 1 - 1e-6]): wider windows are refused, not mis-indexed
+  // (full recompute has no window).
+  if (!(flags & SMCDET_MH_FULL_RECOMPUTE) && model->W > 256 &&
+      2.0f * model->psf_radius + 2.0f + 4.8f * mh->locs_stdev > 256.0f)
+    return set_error(SMCDET_EUNSUPPORTED,
+                     "tile width %d with psf_radius %d and locs_stdev %g: union windows could "
+                     "exceed 256 columns", model->W, model->psf_radius, (double)mh->locs_stdev);
 
   MhArgs a{};
   a.m = make_dev_model(*model);

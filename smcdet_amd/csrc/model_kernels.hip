@@ -171,7 +171,7 @@ __device__ float poisson_draw(float lam, uint32_t k0, uint32_t k1, uint32_t c0, 
       if (ctr > 4096) return (float)k;
     }
   }
-  const float slam = sqrtf(lam), loglam = logf(lam);
+  const float slam = sqrtf(lam);
   const float b = 0.931f + 2.53f * slam;
   const float a = -0.059f + 0.02483f * b;
   const float inv_alpha = 1.1239f + 1.1328f / (b - 3.4f);
@@ -184,7 +184,13 @@ __device__ float poisson_draw(float lam, uint32_t k0, uint32_t k1, uint32_t c0, 
     const float k = floorf((2.f * a / us + b) * U + lam + 0.43f);
     if (us >= 0.07f && V <= vr) return k;
     if (k < 0.f || (us < 0.013f && V > us)) continue;
-    if (logf(V) + logf(inv_alpha) - logf(a / (us * us) + b) <= -lam + k * loglam - lgammaf(k + 1.f))
+    // the squeeze failed (rare): the exact test in double.  Its right side is a
+    // difference of terms near lam * log(lam) (2e6 at lam = 3e5, float32 ulp
+    // 0.25), so in float32 the decision is noise above lam ~ 1e5 and the draws
+    // come out over-dispersed (variance / lam 1.05 at 1e6).
+    const double kd = (double)k;
+    if (log((double)V) + log((double)inv_alpha) - log((double)a / ((double)us * us) + (double)b) <=
+        -(double)lam + kd * log((double)lam) - lgamma(kd + 1.0))
       return k;
   }
   return lam;
@@ -307,7 +313,9 @@ int smcdet_loglik(const smcdet_image_model_t* model, const float* tiled_image, c
                   void* stream) {
   int rc = validate_model(model, kMaxGlobalPixels);
   if (rc) return rc;
-  if (!tiled_image || !locs || !fluxes || !out) return set_error(SMCDET_EINVAL, "null buffer");
+  // (S = 0: the catalog buffers are empty, never read, and may be null)
+  if (!tiled_image || !out || (S > 0 && (!locs || !fluxes)))
+    return set_error(SMCDET_EINVAL, "null buffer");
   if (T <= 0 || N <= 0 || S < 0)
     return set_error(SMCDET_EUNSUPPORTED, "T=%d N=%d S=%d (need T,N>0, S>=0)", T, N, S);
   if (T > 65535) return set_error(SMCDET_EUNSUPPORTED, "T=%d > 65535", T);
@@ -350,7 +358,7 @@ int smcdet_render(const smcdet_image_model_t* model, const float* locs, const fl
                   int32_t T, int32_t N, int32_t S, float* rate, void* stream) {
   int rc = validate_model(model, kMaxGlobalPixels);
   if (rc) return rc;
-  if (!locs || !fluxes || !rate) return set_error(SMCDET_EINVAL, "null buffer");
+  if (!rate || (S > 0 && (!locs || !fluxes))) return set_error(SMCDET_EINVAL, "null buffer");
   if (T <= 0 || N <= 0 || S < 0 || T > 65535)
     return set_error(SMCDET_EUNSUPPORTED, "T=%d N=%d S=%d", T, N, S);
   const DevModel m = make_dev_model(*model);

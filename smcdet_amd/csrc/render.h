@@ -84,7 +84,9 @@ template <int MODEL, int PPL>
 __device__ __forceinline__ void render_regs(const DevModel& m, float (&lamk)[PPL], float sh,
                                             float sw, float sf, int S, int lane) {
   const int HW = m.H * m.W;
-  const unsigned magic = (65536u + (unsigned)m.W - 1u) / (unsigned)m.W;  // p / W, p < 1024
+  // p / W as (p * ceil(2^20 / W)) >> 20: exact for every W <= 1024, p < 1024
+  // (a 16-bit reciprocal is not: 8x104 puts pixel 831 in row 8); fits __umul24
+  const unsigned magic = ((1u << 20) + (unsigned)m.W - 1u) / (unsigned)m.W;
 #pragma unroll
   for (int k = 0; k < PPL; ++k) lamk[k] = m.bg;
   const float scale = m.g * psf_scale<MODEL>(m);
@@ -99,7 +101,7 @@ __device__ __forceinline__ void render_regs(const DevModel& m, float (&lamk)[PPL
     for (int k = 0; k < PPL; ++k) {
       if (k >= klo && k <= khi) {
         const int p = k * kWave + lane;
-        const int ph = (int)(__umul24((unsigned)p, magic) >> 16);
+        const int ph = (int)(__umul24((unsigned)p, magic) >> 20);
         const int pw = p - (int)__umul24((unsigned)ph, (unsigned)m.W);
         const float dh = ((float)ph + 0.5f) - h;
         const float dw = ((float)pw + 0.5f) - w;

@@ -11,10 +11,10 @@ the mean pruned flux, each against the pooled standard error of the two means.
 Pre-registered gates (tests/test_gpu_statistical.py::test_c2_count_posterior,
 fixed in the commit that added them, before any GPU run of it):
   * every bin: |mean_a - mean_b| <= 3 pooled SE;
-  * total variation <= 0.05 (SURVEY.md §8d) against the 648-run oracle target;
+  * total variation <= 0.05 (SURVEY.md §8d) against the recorded oracle target;
   * pruned mean total flux within 3 pooled SE.
 `var_floor`: per-bin per-run variances that the target side's SE may not go
-below -- for the 20 reference runs, the 648-run oracle target's (20 runs of a
+below -- for the 20 reference runs, the recorded oracle target's (20 runs of a
 law whose lower mode, ~13% of runs, carries most of bins 2-3 underestimate
 those bins' spread: the reference's own bin-2 mean sits 4.2 pooled SE from the
 oracle's, computed from the two fixtures alone).

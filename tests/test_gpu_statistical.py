@@ -237,7 +237,7 @@ def test_c2_count_posterior():
     the pruned posterior mean total flux (sampler.py:262-266), over 256 GPU
     runs of SMCsampler at C2 (32x32 M71 tile, S = 10, N = 4096, K = 100,
     systematic, rho = 0.5) against
-      * the 648 float64 oracle runs (stats_c2_moderate_4096_k100_oracle.json),
+      * the recorded float64 oracle runs (stats_c2_moderate_4096_k100_oracle.json),
       * the reference's own 20 runs (stats_c2_moderate_4096_k100.json).
     Gates, pre-registered (tests/_stats.py; fixed before this test ran on a
     GPU): every bin within 3 pooled SE of both targets (the reference side's

@@ -1,13 +1,13 @@
 """tests/_stats.py on the two recorded C2 K = 100 targets (CPU, fixtures only).
 
 Pins the facts the count-posterior gate's variance floor rests on: the
-reference's 20 runs against the 648 float64 oracle runs put bin 2 (two
+reference's 20 runs against the recorded float64 oracle runs put bin 2 (two
 detectable stars, carried by the lower log Z mode) 4.2 pooled SE apart with the
 20 runs' own variance, inside 3 SE once the reference side's per-run variance
 is floored at the oracle's; the other bins and the pruned flux agree within
 2 SE either way.  Total variation between a 20-run mean histogram and the
 target is noise-dominated (0.077), which is why the TV gate is against the
-648-run target only.
+recorded oracle target only.
 """
 import json
 import os
