@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMCDET_ABI_VERSION 19
+#define SMCDET_ABI_VERSION 20
 
 /* status codes */
 #define SMCDET_OK 0
@@ -542,6 +542,103 @@ int smcdet_match_catalogs(const int32_t* true_counts, const float* true_locs,
                           float* true_matches, float* est_total,
                           float* est_matches, int32_t* match_of_true,
                           void* stream);
+
+/* ---- condensed catalogs --------------------------------- */
+/* A run leaves N equally weighted (or weighted) catalogs per tile; these three
+ * entry points, with smcdet_match_catalogs between the second and the third,
+ * condense them into one list of detections per tile.  The reference has no
+ * counterpart (its notebooks scatter-plot the sampled locations by hand).
+ *
+ * Layouts as smcdet_match_catalogs: counts [T,N] int32, locs [T,N,S,2],
+ * fluxes [T,N,S], kept sources first; weights [T,N] (nullable: every catalog
+ * weighs 1).  Source (t, n, j) is *counted* iff j < clamp(counts[t,n], 0, S),
+ * both coordinates are finite and the flux is finite and > 0 -- the rule of
+ * smcdet_match_catalogs; padding may hold anything, NaN included.
+ * `box` is a HOST pointer to four floats (lo_h, lo_w, hi_h, hi_w), read
+ * during the call: the location box every tile shares.  tile_boxes (nullable,
+ * device [T,4]) replaces it per tile, as elsewhere in this header. */
+#define SMCDET_MAP_MAX_CELLS_PER_PIXEL 8
+#define SMCDET_MAP_MAX_GRID 2048     /* Gh, Gw of smcdet_source_map */
+#define SMCDET_PEAKS_MAX_CELLS 32768 /* Gh*Gw of smcdet_map_peaks (128 KiB of LDS) */
+#define SMCDET_PEAKS_MAX_SMOOTH 8    /* smooth_radius, cells */
+#define SMCDET_PEAKS_MAX_NMS 16      /* nms_radius, cells */
+#define SMCDET_SEED_MOMENTS 10       /* float64 sums per seed of smcdet_seed_moments */
+
+/* Posterior source-density map on a grid of c = cells_per_pixel (1..8) cells
+ * per pixel, Gh x Gw cells per tile, cell (0,0) at the box's lower corner.
+ * The cell of a counted source at (h, w) is, in float32 exactly as written,
+ *   ih = floorf((h - lo_h) * (float)c),  iw = floorf((w - lo_w) * (float)c),
+ * and it lies in the grid iff 0 <= ih < Gh and 0 <= iw < Gw.
+ *   count_map [T,Gh,Gw]           sum of the weights of the counted sources per cell
+ *   flux_map  [T,Gh,Gw] nullable  sum of weight * flux (the float32 product) per cell
+ *   outside   [T]                 weight of the counted sources in no cell
+ * The outputs are zeroed here (memsets on `stream`) before the launch.
+ * Each workgroup bins a chunk of one tile's particles into an LDS copy of the
+ * grid (up to 160 KiB for the one or two maps) and flushes its non-zero cells
+ * with float atomic adds; a larger grid is added to in global memory directly.
+ * Reproducibility: with weights == NULL every cell of count_map and outside is
+ * an integer below 2^24, hence exact and identical on every run whatever the
+ * arrival order.  With weights, and for flux_map always, the float32 adds
+ * arrive in an order that varies, so the last bits may differ between runs.
+ * cells_per_pixel outside 1..8, Gh or Gw > SMCDET_MAP_MAX_GRID, or N*S above
+ * 2^31-1: SMCDET_EUNSUPPORTED before any device work; a null required buffer,
+ * a size < 1 or (without tile_boxes) a box that is not finite with lo < hi:
+ * SMCDET_EINVAL. */
+int smcdet_source_map(const int32_t* counts, const float* locs,
+                      const float* fluxes, const float* weights,
+                      const float* box, const float* tile_boxes, int32_t T,
+                      int32_t N, int32_t S, int32_t cells_per_pixel, int32_t Gh,
+                      int32_t Gw, float* count_map, float* flux_map,
+                      float* outside, void* stream);
+
+/* Seeds: the peaks of map [T,Gh,Gw].  With q = smooth_radius (0..8) and p =
+ * nms_radius (0..16), in cells:
+ *   s[i,j] = sum of map over the (2q+1)^2 window around (i,j), the map taken
+ *   as zero outside the grid (float32, summed row by row);
+ *   cell x is a peak iff s[x] >= min_mass[t], s[x] > 0 and, for every other
+ *   cell y of the grid within Chebyshev distance p, s[x] > s[y], or s[x] ==
+ *   s[y] and the flat index i*Gw + j of x is below that of y.
+ * min_mass [T] is a device array.  The peaks are ordered by descending s, then
+ * ascending flat index, and the first K (<= SMCDET_MATCH_MAX_SOURCES) kept:
+ *   n_seeds   [T]     int32  number of seeds kept
+ *   seed_cell [T,K]   int32  flat cell index; -1 past n_seeds
+ *   seed_mass [T,K]          s at the peak; 0 past n_seeds
+ *   seed_locs [T,K,2]        NaN past n_seeds; else the mass-weighted centroid
+ *       of the raw map over the peak's (2q+1)^2 window clipped to the grid, in
+ *       pixels: lo + (sum m*(i+0.5) / sum m) / c, formed in float64 and
+ *       rounded once.
+ * One workgroup per tile, the smoothed map in LDS: Gh*Gw above
+ * SMCDET_PEAKS_MAX_CELLS is SMCDET_EUNSUPPORTED (use a smaller
+ * cells_per_pixel), as are K, cells_per_pixel and the radii outside their
+ * ranges; null buffers and sizes < 1 are SMCDET_EINVAL.  Deterministic. */
+int smcdet_map_peaks(const float* map, const float* box,
+                     const float* tile_boxes, int32_t T, int32_t Gh, int32_t Gw,
+                     int32_t cells_per_pixel, int32_t smooth_radius,
+                     int32_t nms_radius, const float* min_mass, int32_t K,
+                     int32_t* n_seeds, int32_t* seed_cell, float* seed_mass,
+                     float* seed_locs, void* stream);
+
+/* Per-seed posterior moments.  match_of_seed [T,N,K] int32 is the
+ * match_of_true output of smcdet_match_catalogs with the seeds as the true
+ * catalog: the slot of catalog n matched to seed k, or -1.  seed_locs [T,K,2].
+ * moments [T,K,SMCDET_SEED_MOMENTS] is FLOAT64 (double): sums over the
+ * catalogs n with 0 <= match_of_seed[t,n,k] < S, w the catalog's weight (or
+ * 1), every operand converted to double before any arithmetic, with
+ * dh = (double)h - (double)seed_h, dw likewise, f the matched flux and
+ * m = 22.5 - 2.5 log10((double)f):
+ *   0 sum w      1 sum w dh    2 sum w dw    3 sum w dh^2   4 sum w dw^2
+ *   5 sum w dh dw   6 sum w f   7 sum w f^2   8 sum w m     9 sum w m^2
+ * matched_flux [T,N,K] float32 (nullable): the matched source's flux, NaN when
+ * unmatched.  One workgroup per tile; each lane accumulates one seed over a
+ * fixed stride of catalogs in float64 and the lanes of a seed are then added
+ * in lane order, so the result is identical on every run.
+ * K or S above SMCDET_MATCH_MAX_SOURCES: SMCDET_EUNSUPPORTED; null required
+ * buffers and sizes < 1: SMCDET_EINVAL. */
+int smcdet_seed_moments(const int32_t* match_of_seed, const float* locs,
+                        const float* fluxes, const float* weights,
+                        const float* seed_locs, int32_t T, int32_t N, int32_t S,
+                        int32_t K, double* moments, float* matched_flux,
+                        void* stream);
 
 /* ---- tile aggregation (smcdet/aggregate.py:8-593, Aggregate) ------------- */
 #define SMCDET_AGG_MAX_SOURCES 4096

@@ -143,6 +143,40 @@ int main() {
                                d, d, d, nullptr, nullptr), SMCDET_EUNSUPPORTED);
   EXPECT(smcdet_match_catalogs(ws, d, d, ws, d, d, nullptr, 1, 1, 1, 4, 4, 0.5f, 0.5f, d, 65, d,
                                d, d, d, nullptr, nullptr), SMCDET_EUNSUPPORTED);
+  // condensed catalogs: null buffers, sizes, a bad box, limits (box is a host pointer)
+  const float box[4] = {-2.f, -2.f, 10.f, 10.f}, nobox[4] = {0.f, 0.f, 0.f, 8.f};
+  EXPECT(smcdet_source_map(nullptr, d, d, nullptr, box, nullptr, 1, 4, 3, 4, 48, 48, d, nullptr, d,
+                           nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_source_map(ws, d, d, nullptr, nullptr, nullptr, 1, 4, 3, 4, 48, 48, d, nullptr, d,
+                           nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_source_map(ws, d, d, nullptr, nobox, nullptr, 1, 4, 3, 4, 48, 48, d, nullptr, d,
+                           nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_source_map(ws, d, d, nullptr, box, nullptr, 1, 0, 3, 4, 48, 48, d, nullptr, d,
+                           nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_source_map(ws, d, d, nullptr, box, nullptr, 1, 4, 3, 9, 48, 48, d, nullptr, d,
+                           nullptr), SMCDET_EUNSUPPORTED);
+  EXPECT(smcdet_source_map(ws, d, d, nullptr, box, nullptr, 1, 4, 3, 4, 2049, 48, d, nullptr, d,
+                           nullptr), SMCDET_EUNSUPPORTED);
+  EXPECT(smcdet_source_map(ws, d, d, nullptr, box, nullptr, 1, 1 << 30, 3, 4, 48, 48, d, nullptr,
+                           d, nullptr), SMCDET_EUNSUPPORTED);
+  EXPECT(smcdet_map_peaks(d, box, nullptr, 1, 48, 48, 4, 1, 2, nullptr, 20, ws, ws, d, d, nullptr),
+         SMCDET_EINVAL);
+  EXPECT(smcdet_map_peaks(d, box, nullptr, 1, 48, 48, 4, 1, 2, d, 0, ws, ws, d, d, nullptr),
+         SMCDET_EINVAL);
+  EXPECT(smcdet_map_peaks(d, box, nullptr, 1, 48, 48, 4, 1, 2, d, 65, ws, ws, d, d, nullptr),
+         SMCDET_EUNSUPPORTED);
+  EXPECT(smcdet_map_peaks(d, box, nullptr, 1, 182, 182, 4, 1, 2, d, 20, ws, ws, d, d, nullptr),
+         SMCDET_EUNSUPPORTED);
+  EXPECT(smcdet_map_peaks(d, box, nullptr, 1, 48, 48, 4, 9, 2, d, 20, ws, ws, d, d, nullptr),
+         SMCDET_EUNSUPPORTED);
+  EXPECT(smcdet_map_peaks(d, box, nullptr, 1, 48, 48, 4, 1, 17, d, 20, ws, ws, d, d, nullptr),
+         SMCDET_EUNSUPPORTED);
+  EXPECT(smcdet_seed_moments(ws, d, d, nullptr, d, 1, 4, 3, 20, nullptr, nullptr, nullptr),
+         SMCDET_EINVAL);
+  EXPECT(smcdet_seed_moments(ws, d, d, nullptr, d, 1, 4, 0, 20, (double*)d, nullptr, nullptr),
+         SMCDET_EINVAL);
+  EXPECT(smcdet_seed_moments(ws, d, d, nullptr, d, 1, 4, 3, 65, (double*)d, nullptr, nullptr),
+         SMCDET_EUNSUPPORTED);
   EXPECT(smcdet_count_posterior(d, d, 0, 1, 100000, 4, 1, 4, SMCDET_RESAMPLE_SYSTEMATIC, 0, 0,
                                 nullptr, nullptr, d, d, d, d, idx, d, d, d, nullptr),
          SMCDET_EUNSUPPORTED);

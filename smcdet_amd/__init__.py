@@ -4,6 +4,8 @@ Drop-in for the hot path of timwhite0/smcdet: the modules `sampler`,
 `kernel`, `images`, `prior`, `distributions`, `metrics` keep the reference's classes
 and signatures; the per-particle work runs as hand-written HIP kernels behind
 the C ABI in include/smcdet_hip.h (libsmcdet_hip.so, loaded by ctypes).
+`condense` (not in the reference) turns a run's catalogs into one list of
+detections per tile.
 """
 import importlib
 import sys
@@ -13,7 +15,7 @@ from . import _hip  # noqa: F401
 __version__ = "0.1.0"
 
 _DROP_IN = ("sampler", "kernel", "images", "prior", "distributions", "aggregate",
-            "metrics")
+            "metrics", "condense")
 
 
 def install_as_smcdet():

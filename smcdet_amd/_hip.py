@@ -25,7 +25,7 @@ SMCDET_RESAMPLE_SYSTEMATIC = 1
 SMCDET_MH_FULL_RECOMPUTE = 1
 SMCDET_MH_COMPONENT_BY_COUNT = 2
 SMCDET_MH_SKIP_DONE = 4
-ABI_VERSION = 19
+ABI_VERSION = 20
 SMCDET_SMC_FREEZE_DONE = 1
 SMCDET_SMC_TWO_LAUNCH = 2
 
@@ -42,6 +42,12 @@ MAX_PSF_RADIUS = 64
 MAX_AGG_SOURCES = 4096      # sources of an aggregated (joint) tile (LDS or workspace catalog)
 MATCH_MAX_SOURCES = 64      # SMCDET_MATCH_MAX_SOURCES: sources per catalog in match_catalogs
 MATCH_MAX_BINS = 64         # SMCDET_MATCH_MAX_BINS: magnitude bins in match_catalogs
+MAP_MAX_CELLS_PER_PIXEL = 8  # SMCDET_MAP_MAX_CELLS_PER_PIXEL: grid resolution of source_map
+MAP_MAX_GRID = 2048         # SMCDET_MAP_MAX_GRID: cells per side of a source map
+PEAKS_MAX_CELLS = 32768     # SMCDET_PEAKS_MAX_CELLS: cells of a map find_seeds can search
+PEAKS_MAX_SMOOTH = 8        # SMCDET_PEAKS_MAX_SMOOTH: smooth_radius, cells
+PEAKS_MAX_NMS = 16          # SMCDET_PEAKS_MAX_NMS: nms_radius, cells
+SEED_MOMENTS = 10           # SMCDET_SEED_MOMENTS: float64 sums per seed
 
 
 def check_limits(H, W, S, N=None, T=None, R=None, where="sampler", global_ok=False):
@@ -155,6 +161,11 @@ _SIGS = {
     "smcdet_prune": ([c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p], c_i),
     "smcdet_match_catalogs": ([c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f,
                                c_f, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
+    "smcdet_source_map": ([c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p,
+                           c_p, c_p], c_i),
+    "smcdet_map_peaks": ([c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p,
+                          c_p, c_p], c_i),
+    "smcdet_seed_moments": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p], c_i),
     "smcdet_aggregate_sweep": ([c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p,
                                 c_p, c_p, c_p, c_u64, c_u64, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                 c_p], c_i),
@@ -195,6 +206,9 @@ _OUTS = {
     "smcdet_count_posterior": ((16, 17, 18, 19, 20), ()),
     "smcdet_prune": ((7, 8, 9), ()),
     "smcdet_match_catalogs": ((16, 17, 18, 19, 20), ()),
+    "smcdet_source_map": ((12, 13, 14), ()),
+    "smcdet_map_peaks": ((11, 12, 13, 14), ()),
+    "smcdet_seed_moments": ((9, 10), ()),
     "smcdet_aggregate_sweep": ((13, 14, 15, 19, 20, 21, 22, 24), ((10, 13), (11, 14), (12, 15))),
     "smcdet_aggregate_temper": ((10,), ()),
     "smcdet_aggregate_reweight": ((10, 11, 12, 13, 17), ()),
@@ -293,6 +307,7 @@ SOURCES = tuple(os.path.join(_REPO, p) for p in (
     "smcdet_amd/csrc/mh_kernel.hip", "smcdet_amd/csrc/mala_kernel.hip",
     "smcdet_amd/csrc/chain_kernel.hip", "smcdet_amd/csrc/smc_kernels.hip",
     "smcdet_amd/csrc/agg_kernel.hip", "smcdet_amd/csrc/match_kernel.hip",
+    "smcdet_amd/csrc/condense_kernel.hip",
     "smcdet_amd/csrc/device.h", "smcdet_amd/csrc/render.h",
     "smcdet_amd/csrc/mcmc.h", "smcdet_amd/csrc/tile.h", "include/smcdet_hip.h"))
 
