@@ -640,6 +640,59 @@ int smcdet_seed_moments(const int32_t* match_of_seed, const float* locs,
                         int32_t K, double* moments, float* matched_flux,
                         void* stream);
 
+/* ---- posterior-predictive images and model checks -------- */
+/* Does the fitted model reproduce the image?  From the N posterior catalogs of
+ * each tile, with lambda[n,p] the rate smcdet_render defines and
+ * w~[n] = weights[t,n] / sum_n weights[t,n] (weights nullable: uniform; they
+ * must be >= 0 and need not be normalised; a tile whose weights sum to 0 gets
+ * NaN):
+ *   mean [T,H,W]  sum_n w~[n] lambda[n,p]
+ *   var  [T,H,W]  sum_n w~[n] (lambda[n,p] - mean[p])^2  (population form, >= 0)
+ * and per catalog, each output nullable, with v(lambda) = noise_additive +
+ * noise_multiplicative * lambda (M71) or lambda (POISSON), which must be > 0:
+ *   chi2     [T,N]  sum_p (x[p] - lambda)^2 / v(lambda), x = tiled_image
+ *   flux_rep [T,N]  sum_p x_rep[n,p]
+ *   chi2_rep [T,N]  sum_p (x_rep[n,p] - lambda)^2 / v(lambda)
+ * x_rep[n,p] is the draw smcdet_sample_image makes at the same seed and offset
+ * for element i = (t*H*W + p)*N + n of a [T,H,W,N] rate array (Philox counter
+ * offset + i, the same tags and arithmetic), so smcdet_render followed by
+ * smcdet_sample_image and a sum reproduces the two replicate outputs.
+ * tiled_image is needed for chi2 only (chi2 without it: SMCDET_EINVAL).  S = 0
+ * is legal (the rate is the background; locs and fluxes may then be null).
+ * Neither a rate image nor a replicate is stored.  One catalog per wavefront,
+ * rendered as smcdet_loglik renders it (registers up to 1024 pixels and S <=
+ * 64, the per-wave LDS image up to 4096 pixels, 64-pixel chunks above); the
+ * sums over catalogs are float64 sums of w~ (lambda - background) and its
+ * square, the sums over pixels float64 as well; all are rounded to float32 once.
+ * Determinism: each workgroup writes the partial sums of its chunk of
+ * catalogs to `workspace`, a second kernel adds a tile's chunks in chunk
+ * order, and no atomic is used: two calls on the same inputs give
+ * bit-identical outputs, and mean / var do not depend on which of the
+ * per-catalog outputs are requested.
+ * workspace: caller-owned, 16-byte aligned, at least
+ * smcdet_posterior_image_workspace(model, T, N) bytes (contents on entry are
+ * ignored).  With C = min(ceil(N/32), 64) (above 4096 pixels:
+ * C = 4 min(ceil(N/4), 64, max(1, 2^20 / (H W)))) that is 8 T + 16 T C H W;
+ * the catalogs of a tile are split into ceil(N / (4 ceil(N / (4 C')))) chunks,
+ * C' = C (above 4096 pixels: C / 4).  The function returns a negative SMCDET_E*
+ * code for a model or shape smcdet_posterior_image refuses.
+ * Limits as smcdet_loglik, all SMCDET_EUNSUPPORTED: T <= 65535, the POISSON
+ * model up to 4096 pixels, S <= 64 above 4096 pixels; T, N < 1 or S < 0
+ * likewise.  A null required buffer (mean, var, workspace; locs / fluxes when
+ * S > 0) or a workspace smaller than required (the message names the size):
+ * SMCDET_EINVAL.  Everything is checked before any device work.
+ * Both entry points were added under SMCDET_ABI_VERSION 20 (purely additive:
+ * no existing entry point or struct changed). */
+int64_t smcdet_posterior_image_workspace(const smcdet_image_model_t* model,
+                                         int32_t T, int32_t N);
+int smcdet_posterior_image(const smcdet_image_model_t* model,
+                           const float* tiled_image, const float* locs,
+                           const float* fluxes, const float* weights, int32_t T,
+                           int32_t N, int32_t S, uint64_t seed, uint64_t offset,
+                           float* mean, float* var, float* chi2,
+                           float* chi2_rep, float* flux_rep, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+
 /* ---- tile aggregation (smcdet/aggregate.py:8-593, Aggregate) ------------- */
 #define SMCDET_AGG_MAX_SOURCES 4096
 

@@ -177,6 +177,31 @@ int main() {
          SMCDET_EINVAL);
   EXPECT(smcdet_seed_moments(ws, d, d, nullptr, d, 1, 4, 3, 65, (double*)d, nullptr, nullptr),
          SMCDET_EUNSUPPORTED);
+  // posterior-predictive images: every call stops before the launch (the
+  // last ones at a workspace one byte short)
+  EXPECT(smcdet_posterior_image_workspace(nullptr, 1, 4), SMCDET_EINVAL);
+  EXPECT(smcdet_posterior_image_workspace(&m, 0, 4), SMCDET_EUNSUPPORTED);
+  EXPECT(smcdet_posterior_image_workspace(&m, 70000, 4), SMCDET_EUNSUPPORTED);
+  EXPECT(smcdet_posterior_image(nullptr, d, d, d, nullptr, 1, 4, 3, 0, 0, d, d, d, d, d, d, 0,
+                                nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_posterior_image(&m, d, d, d, nullptr, 1, 4, 3, 0, 0, nullptr, d, d, d, d, d, 0,
+                                nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_posterior_image(&m, d, d, d, nullptr, 1, 4, 3, 0, 0, d, d, d, d, d, nullptr, 0,
+                                nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_posterior_image(&m, d, nullptr, d, nullptr, 1, 4, 3, 0, 0, d, d, d, d, d, d, 0,
+                                nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_posterior_image(&m, nullptr, d, d, nullptr, 1, 4, 3, 0, 0, d, d, d, d, d, d, 0,
+                                nullptr), SMCDET_EINVAL);
+  EXPECT(smcdet_posterior_image(&m, d, d, d, nullptr, 1, 0, 3, 0, 0, d, d, d, d, d, d, 0,
+                                nullptr), SMCDET_EUNSUPPORTED);
+  EXPECT(smcdet_posterior_image(&m, d, d, d, nullptr, 1, 4, -1, 0, 0, d, d, d, d, d, d, 0,
+                                nullptr), SMCDET_EUNSUPPORTED);
+  {
+    const int64_t need = smcdet_posterior_image_workspace(&m, 3, 257);
+    EXPECT(need == 8 * 3 + 16 * 3 * 9 * 1024 ? 0 : 1, 0);
+    EXPECT(smcdet_posterior_image(&m, nullptr, nullptr, nullptr, d, 3, 257, 0, 0, 0, d, d, nullptr,
+                                  d, d, d, need - 1, nullptr), SMCDET_EINVAL);
+  }
   EXPECT(smcdet_count_posterior(d, d, 0, 1, 100000, 4, 1, 4, SMCDET_RESAMPLE_SYSTEMATIC, 0, 0,
                                 nullptr, nullptr, d, d, d, d, idx, d, d, d, nullptr),
          SMCDET_EUNSUPPORTED);

@@ -5,7 +5,8 @@ Drop-in for the hot path of timwhite0/smcdet: the modules `sampler`,
 and signatures; the per-particle work runs as hand-written HIP kernels behind
 the C ABI in include/smcdet_hip.h (libsmcdet_hip.so, loaded by ctypes).
 `condense` (not in the reference) turns a run's catalogs into one list of
-detections per tile.
+detections per tile; `predictive` (not in the reference either) gives the
+posterior mean / variance image and posterior-predictive checks of a run.
 """
 import importlib
 import sys
@@ -15,7 +16,7 @@ from . import _hip  # noqa: F401
 __version__ = "0.1.0"
 
 _DROP_IN = ("sampler", "kernel", "images", "prior", "distributions", "aggregate",
-            "metrics", "condense")
+            "metrics", "condense", "predictive")
 
 
 def install_as_smcdet():

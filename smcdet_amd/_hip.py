@@ -166,6 +166,9 @@ _SIGS = {
     "smcdet_map_peaks": ([c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p,
                           c_p, c_p], c_i),
     "smcdet_seed_moments": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p], c_i),
+    "smcdet_posterior_image_workspace": ([c_p, c_i, c_i], c_i64),
+    "smcdet_posterior_image": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_u64, c_u64, c_p, c_p,
+                                c_p, c_p, c_p, c_p, c_i64, c_p], c_i),
     "smcdet_aggregate_sweep": ([c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p,
                                 c_p, c_p, c_p, c_u64, c_u64, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                 c_p], c_i),
@@ -209,6 +212,8 @@ _OUTS = {
     "smcdet_source_map": ((12, 13, 14), ()),
     "smcdet_map_peaks": ((11, 12, 13, 14), ()),
     "smcdet_seed_moments": ((9, 10), ()),
+    "smcdet_posterior_image_workspace": ((), ()),
+    "smcdet_posterior_image": ((10, 11, 12, 13, 14, 15), ()),
     "smcdet_aggregate_sweep": ((13, 14, 15, 19, 20, 21, 22, 24), ((10, 13), (11, 14), (12, 15))),
     "smcdet_aggregate_temper": ((10,), ()),
     "smcdet_aggregate_reweight": ((10, 11, 12, 13, 17), ()),
@@ -307,7 +312,7 @@ SOURCES = tuple(os.path.join(_REPO, p) for p in (
     "smcdet_amd/csrc/mh_kernel.hip", "smcdet_amd/csrc/mala_kernel.hip",
     "smcdet_amd/csrc/chain_kernel.hip", "smcdet_amd/csrc/smc_kernels.hip",
     "smcdet_amd/csrc/agg_kernel.hip", "smcdet_amd/csrc/match_kernel.hip",
-    "smcdet_amd/csrc/condense_kernel.hip",
+    "smcdet_amd/csrc/condense_kernel.hip", "smcdet_amd/csrc/predictive_kernel.hip",
     "smcdet_amd/csrc/device.h", "smcdet_amd/csrc/render.h",
     "smcdet_amd/csrc/mcmc.h", "smcdet_amd/csrc/tile.h", "include/smcdet_hip.h"))
 

@@ -153,6 +153,62 @@ enum RngTag : uint32_t {
 };
 
 // ---------------------------------------------------------------------------
+// noise draws of smcdet_sample_image (model_kernels.hip) and of the replicate
+// images of smcdet_posterior_image (predictive_kernel.hip): one definition, so
+// the two draw the same value from the same counter
+// ---------------------------------------------------------------------------
+__device__ inline float std_normal(uint32_t a, uint32_t b) {
+  const float u1 = ((float)(a >> 8) + 0.5f) * 5.9604644775390625e-08f;  // (0,1)
+  const float u2 = u01(b);
+  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+}
+
+// PTRS (Hormann 1993) for lambda >= 10, multiplication method below
+__device__ inline float poisson_draw(float lam, uint32_t k0, uint32_t k1, uint32_t c0,
+                                     uint32_t c1) {
+  if (!(lam > 0.f)) return 0.f;
+  uint32_t ctr = 0;
+  if (lam < 10.f) {
+    const float L = expf(-lam);
+    float p = 1.f;
+    int k = -1;
+    while (true) {
+      U4 r = philox4x32(c0, c1, ctr++, kTagNoise + 1, k0, k1);
+      const uint32_t ws[4] = {r.x, r.y, r.z, r.w};
+      for (int i = 0; i < 4; ++i) {
+        ++k;
+        p *= u01(ws[i]);
+        if (p <= L) return (float)k;
+      }
+      if (ctr > 4096) return (float)k;
+    }
+  }
+  const float slam = sqrtf(lam);
+  const float b = 0.931f + 2.53f * slam;
+  const float a = -0.059f + 0.02483f * b;
+  const float inv_alpha = 1.1239f + 1.1328f / (b - 3.4f);
+  const float vr = 0.9277f - 3.6224f / (b - 2.f);
+  while (ctr < 100000) {
+    U4 r = philox4x32(c0, c1, ctr++, kTagNoise + 2, k0, k1);
+    const float U = u01(r.x) - 0.5f;
+    const float V = ((float)(r.y >> 8) + 0.5f) * 5.9604644775390625e-08f;
+    const float us = 0.5f - fabsf(U);
+    const float k = floorf((2.f * a / us + b) * U + lam + 0.43f);
+    if (us >= 0.07f && V <= vr) return k;
+    if (k < 0.f || (us < 0.013f && V > us)) continue;
+    // the squeeze failed (rare): the exact test in double.  Its right side is a
+    // difference of terms near lam * log(lam) (2e6 at lam = 3e5, float32 ulp
+    // 0.25), so in float32 the decision is noise above lam ~ 1e5 and the draws
+    // come out over-dispersed (variance / lam 1.05 at 1e6).
+    const double kd = (double)k;
+    if (log((double)V) + log((double)inv_alpha) - log((double)a / ((double)us * us) + (double)b) <=
+        -(double)lam + kd * log((double)lam) - lgamma(kd + 1.0))
+      return k;
+  }
+  return lam;
+}
+
+// ---------------------------------------------------------------------------
 // wave helpers
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void wave_sync() {
