@@ -223,6 +223,11 @@ __device__ __forceinline__ float readlane(float v, int lane) {
 __device__ __forceinline__ int readlane(int v, int lane) {
   return __builtin_amdgcn_readlane(v, lane);
 }
+// a value every lane of the wave holds alike, as the first lane's (an SGPR):
+// tells the compiler what it cannot prove, so control flow on it is scalar
+__device__ __forceinline__ float wave_uniform(float v) {
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
 // v with lane `lane` replaced by the wave-uniform x
 __device__ __forceinline__ float writelane(float x, int lane, float v) {
   return (int)(threadIdx.x & 63) == lane ? x : v;

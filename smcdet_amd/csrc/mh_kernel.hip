@@ -523,12 +523,17 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
                                 a.anc_bins + (size_t)a.T * (N + 1) + (size_t)t * kBinsCoarse, N,
                                 a.anc_bins[(size_t)a.T * N + t], n);
   if constexpr (GL) lam = a.rate_out + pid * (size_t)HWp;
-  const float count = a.counts_in[src];
+  // One particle per wavefront: every lane loads the same count (src depends
+  // on the wave, not the lane), which the compiler cannot prove.  Taken from
+  // the first lane once, here, Sj, K and with them the whole iteration loop
+  // (back edge, batch bounds, `dirty`) are scalar instead of an exec-mask
+  // loop on VGPR copies of wave-uniform values.
+  const float count = wave_uniform(a.counts_in[src]);
   if (a.counts_out && lane == 0) a.counts_out[pid] = count;
   // range of the moved component: 0..S-1 (kernel.py:35-37), or 0..count-1
   // for count-stratified populations padded to S sources (count 0: no moves)
   const int Sj = a.by_count ? min(max((int)count, 0), S) : S;
-  const float tau = a.temperature[t];
+  const float tau = wave_uniform(a.temperature[t]);
   // independent stopping: a tile already at temperature 1 keeps its
   // (resampled) particles unchanged (SMCDET_MH_SKIP_DONE)
   const int K = (Sj > 0 && !(a.skip_done && tau >= 1.0f)) ? a.K : 0;
@@ -759,16 +764,19 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
   // leave the SIMD with a single (latency-bound) wave for the last quarter of
   // the sweep.  Waves ahead of the others drop to a lower priority so the four
   // progress together and keep the SIMD saturated to the end.
-  int prio_lvl = 0;
+  // The level is (k * 4) / K, which changes where k reaches ceil(q K / 4):
+  // the loop runs quarter by quarter with the priority set between quarters,
+  // so an iteration carries no division and no level test.  `frozen`: an
+  // edge hit ended the sweep.
   __builtin_amdgcn_s_setprio(3);
-  for (int k = 0; k < K; ++k) {
-    const int lvl = (k * 4) / K;
-    if (lvl != prio_lvl) {
-      prio_lvl = lvl;
-      if (lvl == 1) __builtin_amdgcn_s_setprio(2);
-      else if (lvl == 2) __builtin_amdgcn_s_setprio(1);
-      else __builtin_amdgcn_s_setprio(0);
-    }
+  bool frozen = false;
+  int k = 0;
+  for (int q = 0; q < 4 && !frozen; ++q) {
+    if (q == 1) __builtin_amdgcn_s_setprio(2);
+    else if (q == 2) __builtin_amdgcn_s_setprio(1);
+    else if (q == 3) __builtin_amdgcn_s_setprio(0);
+    const int kend = ((q + 1) * K + 3) >> 2;
+    for (; k < kend; ++k) {  // (one iteration; its body keeps the outer loop's indentation)
     const int kl = k & 63;
     if (kl == 0) refill(k);
     if (k >= batch_k0 + batch_n) compute_batch(k);
@@ -1120,7 +1128,10 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
     // reproduced: U = 0 exactly with an edge hit (probability 2^-24 per hit),
     // where the reference accepts and its cached target becomes -inf, so it
     // accepts every later proposal of the sweep; here the sweep ends.
-    if (edge_hit(P.hast)) break;
+    if (edge_hit(P.hast)) {
+      frozen = true;
+      break;
+    }
     if (accept) {
       if constexpr (FULL) {
         cur_ll = new_ll;
@@ -1141,6 +1152,7 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
       sfx = writelane(P.fn, P.j, sfx);
       dirty |= 1ull << P.j;
     }
+    }  // iterations of the quarter
   }
 
   __builtin_amdgcn_s_setprio(0);
