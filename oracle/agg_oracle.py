@@ -24,8 +24,9 @@ from __future__ import annotations
 import numpy as np
 from scipy.optimize import brentq
 
-from oracle.smc_oracle import (M71Model, BasicModel, log_prior, loglikelihood, tempering_objective,
-                               tn_log_prob, tn_sample)
+from oracle.smc_oracle import (M71Model, BasicModel, log_prior, loglikelihood,
+                               multinomial_resample_index, tempering_objective, tn_log_prob,
+                               tn_sample)
 
 
 def present(counts, S):
@@ -264,6 +265,33 @@ def update_weights_groups(loglik_diff, groups, temperature, temperature_prev, ln
     return wi, W, out
 
 
+def intracount_resample_index(w_intra, groups, u):
+    """aggregate.py:506-515 with the uniforms given: multinomial resampling
+    within each count group by smc_oracle.multinomial_resample_index's rule
+    (float64 running sum of the group's float32 weights rounded per element to
+    float32, target = u * its last element in float32, the first bin above
+    the target, clamped to the group's last particle).  w_intra, u [nH,nW,N];
+    groups[h][w]: the tile's group sizes (contiguous from particle 0, as
+    sort_by_count returns them) or (first particle, size) pairs.  Returns
+    tile-local indices s0 + i, and -1 for a particle of no group."""
+    w_intra = np.asarray(w_intra, np.float32)
+    u = np.asarray(u, np.float32)
+    idx = np.full(w_intra.shape, -1, np.int64)
+    for h in range(w_intra.shape[0]):
+        for w in range(w_intra.shape[1]):
+            s0 = 0
+            for g in groups[h][w]:
+                if np.ndim(g) == 0:
+                    a, n = s0, int(g)
+                    s0 += n
+                else:
+                    a, n = int(g[0]), int(g[1])
+                if n > 0:
+                    idx[h, w, a:a + n] = a + multinomial_resample_index(
+                        w_intra[h, w, a:a + n], u[h, w, a:a + n])
+    return idx
+
+
 def merge_log_evidence(lnc_children, joint_counts, axis):
     """Repaired aggregate.py:362-422.  After the children's particles are
     resampled by their weights and joined, the population is (approximately)
@@ -297,4 +325,5 @@ def merge_log_evidence(lnc_children, joint_counts, axis):
 
 __all__ = ["M71Model", "BasicModel", "present", "compact", "drop_sources_from_overlap", "join",
            "unjoin", "child_model", "parent_child_loglik", "agg_log_target", "agg_mh_sweep",
-           "sort_by_count", "temper_groups", "update_weights_groups", "merge_log_evidence"]
+           "sort_by_count", "temper_groups", "update_weights_groups", "intracount_resample_index",
+           "merge_log_evidence"]

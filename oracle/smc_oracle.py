@@ -499,6 +499,23 @@ def systematic_resample_index(W, U):
     return np.clip(idx, 0, N - 1)
 
 
+def multinomial_resample_index(W, u):
+    """sampler.py:127-140 with the uniforms given: bins = cumsum(W) as in
+    systematic_resample_index (float64 running sum, each element rounded to
+    float32), target = u * bins[-1] formed in float32, idx = the first i with
+    bins[i] > target, clamped to N - 1.  W, u [..., N] -> int64 [..., N]."""
+    W = np.asarray(W, dtype=np.float32)
+    u = np.asarray(u, dtype=np.float32)
+    N = W.shape[-1]
+    bins = np.cumsum(W.astype(np.float64), axis=-1).astype(np.float32)
+    target = (u * bins[..., -1:]).astype(np.float32)
+    b2, t2 = bins.reshape(-1, N), target.reshape(-1, target.shape[-1])
+    idx = np.empty(t2.shape, dtype=np.int64)
+    for r in range(b2.shape[0]):
+        idx[r] = np.searchsorted(b2[r], t2[r], side="right")
+    return np.clip(idx, 0, N - 1).reshape(target.shape)
+
+
 def gather_particles(idx, counts, locs, fluxes):
     """sampler.py:150-169."""
     c = np.take_along_axis(counts, idx, axis=-1)

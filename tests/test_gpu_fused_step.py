@@ -89,6 +89,18 @@ def test_fused_step_equals_split_step_tiles_multinomial():
         a = _sampler(img, 16, 768, 6, 40, 91, method=method, fused_step=True)
         b = _sampler(img, 16, 768, 6, 40, 91, method=method, fused_step=False)
         _assert_same(_steps(a, 5), _steps(b, 5))
+    # masked widths of the tail's 256-thread layout: one 16x16 tile whose
+    # particle counts the two-launch form runs as PER = 2, 4 and 8 with masked
+    # slots (the tail runs its one PER = 8 instantiation on all of them)
+    from smcdet_amd import _hip
+    img = _image(16, 6)
+    for N in (516, 1500, 4092):
+        for method in ("multinomial", "systematic"):
+            a = _sampler(img, 16, N, 6, 10, 91, method=method, fused_step=True)
+            assert _hip.lib().smcdet_mh_sweep_step_fused(
+                _hip.ref(a.ImageModel._cmodel()), N, 6, 0) == 1
+            b = _sampler(img, 16, N, 6, 10, 91, method=method, fused_step=False)
+            _assert_same(_steps(a, 4), _steps(b, 4))
 
 
 def test_fused_run_equals_split_run_independent_stopping():
