@@ -693,6 +693,90 @@ int smcdet_posterior_image(const smcdet_image_model_t* model,
                            float* chi2_rep, float* flux_rep, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* ---- posterior calibration summaries --------------------- */
+/* The three entry points below were added under SMCDET_ABI_VERSION 20 (purely
+ * additive: no existing entry point or struct changed).  None uses a float
+ * atomic and every reduction has a fixed order: two calls on the same inputs
+ * return the same bits. */
+#define SMCDET_TOTALS_MAX_CUTS 8     /* C of smcdet_catalog_totals */
+#define SMCDET_SUMMARY_MAX_N 16384   /* N of smcdet_row_summary (keys + payload: 128 KiB of LDS) */
+#define SMCDET_SUMMARY_MAX_Q 64      /* quantile levels per call */
+#define SMCDET_SUMMARY_MAX_E 65      /* thresholds per row */
+#define SMCDET_SUMMARY_LINEAR 0      /* numpy / torch "linear" quantiles (unweighted only) */
+#define SMCDET_SUMMARY_LOWER 1       /* smallest value whose cumulative weight reaches q * weight */
+#define SMCDET_BOOT_MAX_COLUMNS 256  /* D of smcdet_bootstrap_means */
+
+/* Per-catalog functionals.  counts [T,N] int32, fluxes [T,N,S] (kept sources
+ * first, as smcdet_match_catalogs takes them), flux_cuts: C (1..8) floats in
+ * HOST memory.  With cnt = min(max(counts[t,n], 0), S):
+ *   n_above    [C,T,N] int32  number of slots s < cnt with fluxes[t,n,s] >= flux_cuts[c]
+ *   flux_above [C,T,N]        the sum of those fluxes, accumulated in float64 in
+ *                             slot order and rounded to float32 once
+ * Slots at or past cnt are never looked at, whatever they hold; a NaN inside
+ * the counted slots is above no cut.  One pass over fluxes: a workgroup stages
+ * 256 catalogs x 16 slots at a time through LDS so that global reads are
+ * contiguous, then one thread per catalog walks its slots.
+ * C > SMCDET_TOTALS_MAX_CUTS, S > SMCDET_MATCH_MAX_SOURCES or T*N above 2^31-1:
+ * SMCDET_EUNSUPPORTED; sizes < 1, a null buffer or a NaN cut: SMCDET_EINVAL. */
+int smcdet_catalog_totals(const int32_t* counts, const float* fluxes,
+                          const float* flux_cuts, int32_t T, int32_t N, int32_t S,
+                          int32_t C, int32_t* n_above, float* flux_above,
+                          void* stream);
+
+/* Order statistics along N.  values [A,N,B] float32, summarised along N: a
+ * "row" is one (a, b), and every per-row output is indexed [a,b].  NaN in
+ * values means "missing" and is excluded from everything.  weights [A,N]
+ * (nullable: 1) are >= 0 and shared by the B rows of an a.  q: Q (0..64)
+ * doubles in [0,1] in HOST memory.  thresholds [A,B,E] (device, nullable iff
+ * E = 0, E <= 65).
+ *   n_valid [A,B] int32     entries that are not NaN
+ *   weight  [A,B] float64   sum of the weights of the valid entries (= n_valid without weights)
+ *   mean    [A,B] float64   sum w v / weight
+ *   var     [A,B] float64   sum w (v - mean)^2 / weight, clamped at 0
+ *   vmin, vmax [A,B]        the smallest / largest valid value
+ *   quantiles [A,B,Q]       (nullable iff Q = 0)
+ *   below, at_or_below [A,B,E] float64 (nullable iff E = 0): the weight of the
+ *       valid entries < e and <= e (float comparison: -0 == +0; a NaN threshold gives 0)
+ * A row with weight == 0 (in particular n_valid == 0) gets NaN for mean, var
+ * and the quantiles and 0 for the masses; vmin / vmax are NaN iff n_valid == 0.
+ * SMCDET_SUMMARY_LINEAR (weights must be null): with v the valid entries in
+ * ascending order, pos = q * (n_valid - 1) in float64, lo = floor(pos) and
+ * g = pos - lo: v[lo] when g == 0, else v[lo] + (v[lo+1] - v[lo]) * g formed in
+ * float64 from the two float32 order statistics and rounded to float32 once.
+ * SMCDET_SUMMARY_LOWER: the smallest valid value whose cumulative weight, in
+ * ascending order of (value, index n), is >= q * weight (that float64
+ * product); q = 0 gives the minimum.
+ * One workgroup per row, b fastest in the grid: the row's keys (the float32
+ * mapped to an order-preserving uint32, NaN last; with weights the index n
+ * rides along as the low word of a 64-bit key) are bitonic-sorted in LDS, sized
+ * to the next power of two >= N; the weighted sums are float64, each thread
+ * summing its contiguous sorted segment and one block scan combining them.
+ * N > SMCDET_SUMMARY_MAX_N, Q > SMCDET_SUMMARY_MAX_Q, E > SMCDET_SUMMARY_MAX_E or
+ * A*B above 2^31-1: SMCDET_EUNSUPPORTED; A, N, B < 1, Q or E < 0, a q outside
+ * [0,1], an unknown interpolation, LINEAR with weights, or a null required
+ * buffer: SMCDET_EINVAL.  Everything is checked before any device work. */
+int smcdet_row_summary(const float* values, const float* weights, int32_t A,
+                       int32_t N, int32_t B, const double* q, int32_t Q,
+                       int32_t interpolation, const float* thresholds, int32_t E,
+                       int32_t* n_valid, double* weight, double* mean,
+                       double* var, float* vmin, float* vmax, float* quantiles,
+                       double* below, double* at_or_below, void* stream);
+
+/* Bootstrap row means.  values [M,D] float32 (1 <= D <= 256), out [Bn,D]:
+ *   out[r,d] = (sum_j values[idx[r,j], d]) / M,  j = 0..M-1,
+ * the sum and the quotient in float64, then rounded to float32.  idx is
+ * indices [Bn,M] int32 when given (each in [0,M): NOT checked here), else
+ *   idx[r,j] = mulhi32(x_{j mod 4}, M),  x = Philox4x32-10(counter (r, j / 4, 0,
+ *   tag 0x42530000), key (seed low word, seed high word)),
+ * which favours no index by more than M / 2^32 in probability.  One workgroup
+ * per replicate: lanes run across D, wave groups across draws, and the groups'
+ * float64 partial sums are added through LDS in group order.
+ * D > SMCDET_BOOT_MAX_COLUMNS: SMCDET_EUNSUPPORTED; M, D, Bn < 1 or a null
+ * buffer: SMCDET_EINVAL. */
+int smcdet_bootstrap_means(const float* values, int32_t M, int32_t D,
+                           const int32_t* indices, uint64_t seed, int32_t Bn,
+                           float* out, void* stream);
+
 /* ---- tile aggregation (smcdet/aggregate.py:8-593, Aggregate) ------------- */
 #define SMCDET_AGG_MAX_SOURCES 4096
 

@@ -202,6 +202,41 @@ int main() {
     EXPECT(smcdet_posterior_image(&m, nullptr, nullptr, nullptr, d, 3, 257, 0, 0, 0, d, d, nullptr,
                                   d, d, d, need - 1, nullptr), SMCDET_EINVAL);
   }
+  // calibration summaries: limits, sizes, nulls, and the host arrays (cuts, q)
+  // the validation reads
+  {
+    const float cuts[8] = {0.f, 1.f, 2.f, 3.f, 4.f, 5.f, 6.f, __builtin_nanf("")};
+    const double q[3] = {0.0, 0.5, 1.5};
+    double* dd = (double*)d;
+    EXPECT(smcdet_catalog_totals(ws, d, cuts, 1, 4, 3, 9, ws, d, nullptr), SMCDET_EUNSUPPORTED);
+    EXPECT(smcdet_catalog_totals(ws, d, cuts, 1, 4, 65, 1, ws, d, nullptr), SMCDET_EUNSUPPORTED);
+    EXPECT(smcdet_catalog_totals(ws, d, cuts, 1 << 30, 4, 3, 1, ws, d, nullptr),
+           SMCDET_EUNSUPPORTED);
+    EXPECT(smcdet_catalog_totals(ws, d, cuts, 0, 4, 3, 1, ws, d, nullptr), SMCDET_EINVAL);
+    EXPECT(smcdet_catalog_totals(ws, d, nullptr, 1, 4, 3, 1, ws, d, nullptr), SMCDET_EINVAL);
+    EXPECT(smcdet_catalog_totals(ws, d, cuts, 1, 4, 3, 8, ws, d, nullptr), SMCDET_EINVAL);  // NaN
+    EXPECT(smcdet_row_summary(d, nullptr, 1, 16385, 1, q, 2, SMCDET_SUMMARY_LINEAR, d, 1, ws, dd,
+                              dd, dd, d, d, d, dd, dd, nullptr), SMCDET_EUNSUPPORTED);
+    EXPECT(smcdet_row_summary(d, nullptr, 1, 8, 1, q, 65, SMCDET_SUMMARY_LINEAR, d, 1, ws, dd, dd,
+                              dd, d, d, d, dd, dd, nullptr), SMCDET_EUNSUPPORTED);
+    EXPECT(smcdet_row_summary(d, nullptr, 1, 8, 1, q, 2, SMCDET_SUMMARY_LINEAR, d, 66, ws, dd, dd,
+                              dd, d, d, d, dd, dd, nullptr), SMCDET_EUNSUPPORTED);
+    EXPECT(smcdet_row_summary(d, nullptr, 1 << 20, 8, 1 << 12, q, 2, SMCDET_SUMMARY_LINEAR, d, 1,
+                              ws, dd, dd, dd, d, d, d, dd, dd, nullptr), SMCDET_EUNSUPPORTED);
+    EXPECT(smcdet_row_summary(d, d, 1, 8, 1, q, 2, SMCDET_SUMMARY_LINEAR, d, 1, ws, dd, dd, dd, d,
+                              d, d, dd, dd, nullptr), SMCDET_EINVAL);  // linear with weights
+    EXPECT(smcdet_row_summary(d, nullptr, 1, 8, 1, q, 3, SMCDET_SUMMARY_LOWER, d, 1, ws, dd, dd,
+                              dd, d, d, d, dd, dd, nullptr), SMCDET_EINVAL);  // q = 1.5
+    EXPECT(smcdet_row_summary(d, nullptr, 1, 8, 1, q, 2, 7, d, 1, ws, dd, dd, dd, d, d, d, dd, dd,
+                              nullptr), SMCDET_EINVAL);
+    EXPECT(smcdet_row_summary(d, nullptr, 1, 8, 1, q, 2, SMCDET_SUMMARY_LOWER, nullptr, 1, ws, dd,
+                              dd, dd, d, d, d, dd, dd, nullptr), SMCDET_EINVAL);
+    EXPECT(smcdet_row_summary(d, nullptr, 1, 0, 1, q, 2, SMCDET_SUMMARY_LOWER, d, 1, ws, dd, dd,
+                              dd, d, d, d, dd, dd, nullptr), SMCDET_EINVAL);
+    EXPECT(smcdet_bootstrap_means(d, 4, 257, nullptr, 0, 2, d, nullptr), SMCDET_EUNSUPPORTED);
+    EXPECT(smcdet_bootstrap_means(d, 0, 3, nullptr, 0, 2, d, nullptr), SMCDET_EINVAL);
+    EXPECT(smcdet_bootstrap_means(d, 4, 3, nullptr, 0, 2, nullptr, nullptr), SMCDET_EINVAL);
+  }
   EXPECT(smcdet_count_posterior(d, d, 0, 1, 100000, 4, 1, 4, SMCDET_RESAMPLE_SYSTEMATIC, 0, 0,
                                 nullptr, nullptr, d, d, d, d, idx, d, d, d, nullptr),
          SMCDET_EUNSUPPORTED);

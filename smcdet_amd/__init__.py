@@ -6,7 +6,9 @@ and signatures; the per-particle work runs as hand-written HIP kernels behind
 the C ABI in include/smcdet_hip.h (libsmcdet_hip.so, loaded by ctypes).
 `condense` (not in the reference) turns a run's catalogs into one list of
 detections per tile; `predictive` (not in the reference either) gives the
-posterior mean / variance image and posterior-predictive checks of a run.
+posterior mean / variance image and posterior-predictive checks of a run;
+`calibration` (the reference's results notebooks, by hand) gives count
+posteriors, interval coverage, quantile bands and bootstrap bands.
 """
 import importlib
 import sys
@@ -16,7 +18,7 @@ from . import _hip  # noqa: F401
 __version__ = "0.1.0"
 
 _DROP_IN = ("sampler", "kernel", "images", "prior", "distributions", "aggregate",
-            "metrics", "condense", "predictive")
+            "metrics", "condense", "predictive", "calibration")
 
 
 def install_as_smcdet():

@@ -48,6 +48,14 @@ PEAKS_MAX_CELLS = 32768     # SMCDET_PEAKS_MAX_CELLS: cells of a map find_seeds 
 PEAKS_MAX_SMOOTH = 8        # SMCDET_PEAKS_MAX_SMOOTH: smooth_radius, cells
 PEAKS_MAX_NMS = 16          # SMCDET_PEAKS_MAX_NMS: nms_radius, cells
 SEED_MOMENTS = 10           # SMCDET_SEED_MOMENTS: float64 sums per seed
+TOTALS_MAX_CUTS = 8         # SMCDET_TOTALS_MAX_CUTS: flux cuts of catalog_totals
+SUMMARY_MAX_N = 16384       # SMCDET_SUMMARY_MAX_N: entries per row of row_summary (LDS sort)
+SUMMARY_MAX_Q = 64          # SMCDET_SUMMARY_MAX_Q: quantile levels per call
+SUMMARY_MAX_E = 65          # SMCDET_SUMMARY_MAX_E: thresholds per row
+SUMMARY_LINEAR = 0          # SMCDET_SUMMARY_LINEAR
+SUMMARY_LOWER = 1           # SMCDET_SUMMARY_LOWER
+BOOT_MAX_COLUMNS = 256      # SMCDET_BOOT_MAX_COLUMNS: columns of bootstrap_means
+BOOT_TAG = 0x42530000       # the Philox stream tag of bootstrap_means (device.h kTagBoot)
 
 
 def check_limits(H, W, S, N=None, T=None, R=None, where="sampler", global_ok=False):
@@ -169,6 +177,10 @@ _SIGS = {
     "smcdet_posterior_image_workspace": ([c_p, c_i, c_i], c_i64),
     "smcdet_posterior_image": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_u64, c_u64, c_p, c_p,
                                 c_p, c_p, c_p, c_p, c_i64, c_p], c_i),
+    "smcdet_catalog_totals": ([c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p], c_i),
+    "smcdet_row_summary": ([c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p,
+                            c_p, c_p, c_p, c_p, c_p, c_p], c_i),
+    "smcdet_bootstrap_means": ([c_p, c_i, c_i, c_p, c_u64, c_i, c_p, c_p], c_i),
     "smcdet_aggregate_sweep": ([c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p,
                                 c_p, c_p, c_p, c_u64, c_u64, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                 c_p], c_i),
@@ -214,6 +226,9 @@ _OUTS = {
     "smcdet_seed_moments": ((9, 10), ()),
     "smcdet_posterior_image_workspace": ((), ()),
     "smcdet_posterior_image": ((10, 11, 12, 13, 14, 15), ()),
+    "smcdet_catalog_totals": ((7, 8), ()),
+    "smcdet_row_summary": ((10, 11, 12, 13, 14, 15, 16, 17, 18), ()),
+    "smcdet_bootstrap_means": ((6,), ()),
     "smcdet_aggregate_sweep": ((13, 14, 15, 19, 20, 21, 22, 24), ((10, 13), (11, 14), (12, 15))),
     "smcdet_aggregate_temper": ((10,), ()),
     "smcdet_aggregate_reweight": ((10, 11, 12, 13, 17), ()),
@@ -313,6 +328,7 @@ SOURCES = tuple(os.path.join(_REPO, p) for p in (
     "smcdet_amd/csrc/chain_kernel.hip", "smcdet_amd/csrc/smc_kernels.hip",
     "smcdet_amd/csrc/agg_kernel.hip", "smcdet_amd/csrc/match_kernel.hip",
     "smcdet_amd/csrc/condense_kernel.hip", "smcdet_amd/csrc/predictive_kernel.hip",
+    "smcdet_amd/csrc/summary_kernel.hip",
     "smcdet_amd/csrc/device.h", "smcdet_amd/csrc/render.h",
     "smcdet_amd/csrc/mcmc.h", "smcdet_amd/csrc/tile.h", "include/smcdet_hip.h"))
 

@@ -150,6 +150,7 @@ enum RngTag : uint32_t {
   kTagAgg0 = 0x41470000u,
   kTagAgg1 = 0x41470001u,
   kTagAggResample = 0x41520000u,
+  kTagBoot = 0x42530000u,
 };
 
 // ---------------------------------------------------------------------------
