@@ -777,6 +777,72 @@ int smcdet_bootstrap_means(const float* values, int32_t M, int32_t D,
                            const int32_t* indices, uint64_t seed, int32_t Bn,
                            float* out, void* stream);
 
+/* ---- MCMC convergence diagnostics (added under SMCDET_ABI_VERSION 20) ------
+ * Split-R-hat, effective sample size and Monte Carlo standard error of the
+ * mean for chains of kept draws (Geyer 1992; Vehtari, Gelman, Simpson,
+ * Carpenter & Buerkner 2021, section 3, without the tail term Stan adds to
+ * tau).  The reference has no such diagnostics.  DESIGN.md §14 has the
+ * definitions and the error bounds. */
+#define SMCDET_CHAINS_MAX_CHAINS 32      /* C of smcdet_chain_stats (m = 2C <= 64 split chains) */
+#define SMCDET_CHAINS_MAX_DRAWS 1048576  /* m * n draws of one row */
+#define SMCDET_CHAINS_MAX_RHO 1024       /* num_rho */
+#define SMCDET_CHAINS_LDS_DRAWS 16384    /* rows with m * n <= this keep their draws in LDS */
+#define SMCDET_CHAINS_BLOCK_PAIRS 8      /* lag pairs between two tests of the stopping rule */
+
+/* x [R,C,M] float32: R rows, C chains, M kept draws per chain.  split != 0:
+ * every chain becomes two of length n = M / 2, draws [0, n) and [M - n, M)
+ * (an odd M drops the middle draw, which is never read), m = 2C chains in the
+ * order (chain 0 first half, chain 0 second half, chain 1 first half, ...);
+ * split == 0: m = C, n = M.  n >= 4.  Per chain j, in float64:
+ *   mu_j = mean of its draws,  a_j(t) = (1/n) sum_{i < n-t} (x_i - mu_j)(x_{i+t} - mu_j)
+ * and per row
+ *   mean = mean_j mu_j,  W = mean_j a_j(0) * n / (n - 1),
+ *   B/n = sum_j (mu_j - mean)^2 / (m - 1)  (0 when m = 1),
+ *   var_plus = W (n - 1) / n + B/n,  rhat = sqrt(var_plus / W),
+ *   rho_t = 1 - (W - mean_j a_j(t)) / var_plus,  rho_0 := 1,
+ *   P_k = rho_{2k} + rho_{2k+1} for k = 0, 1, ... while 2k + 1 <= min(n - 1, max_lag);
+ *   the sum stops at the first P_k <= 0 (not included): n_pairs = K pairs kept,
+ *   stopped = 1, or stopped = 0 when the lags ran out; P'_k = min(P'_{k-1}, P_k);
+ *   tau = max(-1 + 2 sum_{k<K} P'_k, 1 / log10(m n)),  ess = m n / tau,
+ *   mcse = sqrt(var_plus / ess).
+ * Row outputs [R]: mean, W, var_plus, rhat, tau, ess, mcse float64; n_pairs,
+ * stopped int32.  Optional (nullable): chain_mean, chain_var [R,m] float64
+ * (mu_j and a_j(0) n / (n - 1)); rho [R,num_rho] float32 (nullable iff num_rho
+ * = 0): rho_0 .. rho_{num_rho-1}, computed whether or not the sum stopped
+ * earlier and whatever max_lag is, NaN for t > n - 1.
+ * A row whose read draws hold a NaN or an infinity gets NaN in every float
+ * output and n_pairs = stopped = 0; a row with W == 0 keeps mean, W, var_plus
+ * and the chain moments and gets NaN for rhat, tau, ess, mcse and rho, n_pairs
+ * = stopped = 0.  A row with W > 0 of which some chains are constant is an
+ * ordinary row.
+ * One workgroup (512 threads) per row.  Phase 1, one wave per chain: the
+ * float64 mean, then the centered draws x_i - mu_j formed in float64 and
+ * rounded to float32 once, and a_j(0) from the unrounded differences.  Phase
+ * 2, SMCDET_CHAINS_BLOCK_PAIRS lag pairs at a time, one pair per wave: lanes
+ * stride over i with float64 accumulators, chains in order, one butterfly over
+ * the lanes per lag; after every block all threads apply the stopping rule to
+ * the same values (workgroup-uniform) and the row ends or takes the next
+ * block.  No atomics: the same bits on every run.  Rows with m n <=
+ * SMCDET_CHAINS_LDS_DRAWS hold the centered draws in LDS (64 KiB: two
+ * workgroups per CU); larger rows keep them in `workspace`, a caller-owned
+ * device buffer of smcdet_chain_stats_workspace() floats (workspace_floats
+ * says how many it holds; nullable when 0 are needed).
+ * C > SMCDET_CHAINS_MAX_CHAINS, m n > SMCDET_CHAINS_MAX_DRAWS, num_rho >
+ * SMCDET_CHAINS_MAX_RHO or R m above 2^31-1: SMCDET_EUNSUPPORTED; R, C, M < 1,
+ * n < 4, max_lag < 1, num_rho < 0, a null required buffer or a workspace
+ * smaller than required: SMCDET_EINVAL.  Everything is checked before any
+ * device work. */
+int smcdet_chain_stats(const float* x, int32_t R, int32_t C, int32_t M,
+                       int32_t split, int32_t max_lag, int32_t num_rho,
+                       double* mean, double* W, double* var_plus, double* rhat,
+                       double* tau, double* ess, double* mcse, int32_t* n_pairs,
+                       int32_t* stopped, double* chain_mean, double* chain_var,
+                       float* rho, float* workspace, int64_t workspace_floats,
+                       void* stream);
+/* Floats of workspace smcdet_chain_stats needs for these shapes (0: the LDS
+ * path runs; < 0: refused, smcdet_last_error says why). */
+int64_t smcdet_chain_stats_workspace(int32_t R, int32_t C, int32_t M, int32_t split);
+
 /* ---- tile aggregation (smcdet/aggregate.py:8-593, Aggregate) ------------- */
 #define SMCDET_AGG_MAX_SOURCES 4096
 

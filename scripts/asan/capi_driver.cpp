@@ -237,6 +237,29 @@ int main() {
     EXPECT(smcdet_bootstrap_means(d, 0, 3, nullptr, 0, 2, d, nullptr), SMCDET_EINVAL);
     EXPECT(smcdet_bootstrap_means(d, 4, 3, nullptr, 0, 2, nullptr, nullptr), SMCDET_EINVAL);
   }
+  // convergence diagnostics: limits, sizes, nulls and the workspace requirement
+  {
+    double* dd = (double*)d;
+#define CHAIN_STATS(R, C, M, split, lag, nrho, x, wsp, wsn)                                  \
+  smcdet_chain_stats(x, R, C, M, split, lag, nrho, dd, dd, dd, dd, dd, dd, dd, ws, ws, nullptr, \
+                     nullptr, d, wsp, wsn, nullptr)
+    EXPECT(CHAIN_STATS(1, 33, 16, 1, 7, 0, d, nullptr, 0), SMCDET_EUNSUPPORTED);
+    EXPECT(CHAIN_STATS(1, 32, 32770, 1, 7, 0, d, nullptr, 0), SMCDET_EUNSUPPORTED);
+    EXPECT(CHAIN_STATS(1, 2, 16, 1, 7, 1025, d, nullptr, 0), SMCDET_EUNSUPPORTED);
+    EXPECT(CHAIN_STATS(1 << 26, 32, 16, 1, 7, 0, d, nullptr, 0), SMCDET_EUNSUPPORTED);
+    EXPECT(CHAIN_STATS(0, 2, 16, 1, 7, 0, d, nullptr, 0), SMCDET_EINVAL);
+    EXPECT(CHAIN_STATS(1, 2, 7, 1, 7, 0, d, nullptr, 0), SMCDET_EINVAL);   // n = 3
+    EXPECT(CHAIN_STATS(1, 2, 16, 1, 0, 0, d, nullptr, 0), SMCDET_EINVAL);  // max_lag
+    EXPECT(CHAIN_STATS(1, 2, 16, 1, 7, -1, d, nullptr, 0), SMCDET_EINVAL);
+    EXPECT(CHAIN_STATS(1, 2, 16, 1, 7, 0, nullptr, nullptr, 0), SMCDET_EINVAL);
+    const int64_t cneed = smcdet_chain_stats_workspace(5, 4, 4098, 1);
+    EXPECT(cneed == 5 * 16392 ? 0 : 1, 0);
+    EXPECT(smcdet_chain_stats_workspace(5, 4, 4096, 1) == 0 ? 0 : 1, 0);
+    EXPECT(smcdet_chain_stats_workspace(1, 33, 16, 1), SMCDET_EUNSUPPORTED);
+    EXPECT(CHAIN_STATS(5, 4, 4098, 1, 7, 0, d, nullptr, 0), SMCDET_EINVAL);
+    EXPECT(CHAIN_STATS(5, 4, 4098, 1, 7, 0, d, d, cneed - 1), SMCDET_EINVAL);
+#undef CHAIN_STATS
+  }
   EXPECT(smcdet_count_posterior(d, d, 0, 1, 100000, 4, 1, 4, SMCDET_RESAMPLE_SYSTEMATIC, 0, 0,
                                 nullptr, nullptr, d, d, d, d, idx, d, d, d, nullptr),
          SMCDET_EUNSUPPORTED);

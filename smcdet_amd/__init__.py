@@ -8,7 +8,9 @@ the C ABI in include/smcdet_hip.h (libsmcdet_hip.so, loaded by ctypes).
 detections per tile; `predictive` (not in the reference either) gives the
 posterior mean / variance image and posterior-predictive checks of a run;
 `calibration` (the reference's results notebooks, by hand) gives count
-posteriors, interval coverage, quantile bands and bootstrap bands.
+posteriors, interval coverage, quantile bands and bootstrap bands;
+`convergence` (not in the reference) gives split-R-hat, effective sample sizes
+and Monte Carlo standard errors of MCMC chains.
 """
 import importlib
 import sys
@@ -18,7 +20,7 @@ from . import _hip  # noqa: F401
 __version__ = "0.1.0"
 
 _DROP_IN = ("sampler", "kernel", "images", "prior", "distributions", "aggregate",
-            "metrics", "condense", "predictive", "calibration")
+            "metrics", "condense", "predictive", "calibration", "convergence")
 
 
 def install_as_smcdet():

@@ -56,6 +56,11 @@ SUMMARY_LINEAR = 0          # SMCDET_SUMMARY_LINEAR
 SUMMARY_LOWER = 1           # SMCDET_SUMMARY_LOWER
 BOOT_MAX_COLUMNS = 256      # SMCDET_BOOT_MAX_COLUMNS: columns of bootstrap_means
 BOOT_TAG = 0x42530000       # the Philox stream tag of bootstrap_means (device.h kTagBoot)
+CHAINS_MAX_CHAINS = 32      # SMCDET_CHAINS_MAX_CHAINS: chains per row of chain_stats (m <= 64)
+CHAINS_MAX_DRAWS = 1048576  # SMCDET_CHAINS_MAX_DRAWS: m * n draws per row
+CHAINS_MAX_RHO = 1024       # SMCDET_CHAINS_MAX_RHO: autocorrelations returned per row
+CHAINS_LDS_DRAWS = 16384    # SMCDET_CHAINS_LDS_DRAWS: rows up to this keep their draws in LDS
+CHAINS_BLOCK_PAIRS = 8      # SMCDET_CHAINS_BLOCK_PAIRS: lag pairs per test of the stopping rule
 
 
 def check_limits(H, W, S, N=None, T=None, R=None, where="sampler", global_ok=False):
@@ -181,6 +186,9 @@ _SIGS = {
     "smcdet_row_summary": ([c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p,
                             c_p, c_p, c_p, c_p, c_p, c_p], c_i),
     "smcdet_bootstrap_means": ([c_p, c_i, c_i, c_p, c_u64, c_i, c_p, c_p], c_i),
+    "smcdet_chain_stats": ([c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                            c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p], c_i),
+    "smcdet_chain_stats_workspace": ([c_i, c_i, c_i, c_i], c_i64),
     "smcdet_aggregate_sweep": ([c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p,
                                 c_p, c_p, c_p, c_u64, c_u64, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                 c_p], c_i),
@@ -229,6 +237,8 @@ _OUTS = {
     "smcdet_catalog_totals": ((7, 8), ()),
     "smcdet_row_summary": ((10, 11, 12, 13, 14, 15, 16, 17, 18), ()),
     "smcdet_bootstrap_means": ((6,), ()),
+    "smcdet_chain_stats": (tuple(range(7, 20)), ()),
+    "smcdet_chain_stats_workspace": ((), ()),
     "smcdet_aggregate_sweep": ((13, 14, 15, 19, 20, 21, 22, 24), ((10, 13), (11, 14), (12, 15))),
     "smcdet_aggregate_temper": ((10,), ()),
     "smcdet_aggregate_reweight": ((10, 11, 12, 13, 17), ()),
@@ -328,7 +338,7 @@ SOURCES = tuple(os.path.join(_REPO, p) for p in (
     "smcdet_amd/csrc/chain_kernel.hip", "smcdet_amd/csrc/smc_kernels.hip",
     "smcdet_amd/csrc/agg_kernel.hip", "smcdet_amd/csrc/match_kernel.hip",
     "smcdet_amd/csrc/condense_kernel.hip", "smcdet_amd/csrc/predictive_kernel.hip",
-    "smcdet_amd/csrc/summary_kernel.hip",
+    "smcdet_amd/csrc/summary_kernel.hip", "smcdet_amd/csrc/convergence_kernel.hip",
     "smcdet_amd/csrc/device.h", "smcdet_amd/csrc/render.h",
     "smcdet_amd/csrc/mcmc.h", "smcdet_amd/csrc/tile.h", "include/smcdet_hip.h"))
 
