@@ -843,6 +843,78 @@ int smcdet_chain_stats(const float* x, int32_t R, int32_t C, int32_t M,
  * path runs; < 0: refused, smcdet_last_error says why). */
 int64_t smcdet_chain_stats_workspace(int32_t R, int32_t C, int32_t M, int32_t split);
 
+/* ---- source-extraction baseline (added under SMCDET_ABI_VERSION 20) --------
+ * The classical detector the reference's experiment scripts compare the SMC
+ * catalogs with (experiments/[name]/run_sep.py: Source Extractor through sep,
+ * grid-searched for F1).  A multi-threshold detector after SExtractor / SEP;
+ * the definition below is this project's own and claims no parity with sep
+ * (differences: DESIGN.md §15).  The reference has no such code of its own. */
+#define SMCDET_EXTRACT_MAX_PIXELS 1024 /* H*W of an image */
+
+/* One problem is image t under setting g; T*G problems, g fastest.
+ * images [T,H,W], background [T], sigma [T] float32; thresh, deblend_cont,
+ * clean_param [G] float32, minarea [G] int32 (>= 1); deblend_nthresh = n, a
+ * power of two in 1..64, for all settings.
+ * Detection values: v = image - background[t] and tau = thresh[g] * sigma[t],
+ *   one float32 operation each.  tau not finite or <= 0: no detections.  A NaN
+ *   pixel is above no threshold.
+ * Roots: the 8-connected components of {v > tau} with >= minarea pixels.
+ * Ladder, float32, correctly rounded operations only: per root with peak p,
+ *   r = p / tau, q = r after log2(n) successive sqrtf, tau_0 = tau,
+ *   tau_k = tau_{k-1} * q (k = 1..n-1).
+ * Significant tree: a node of level k is an 8-connected component of {pixels
+ *   of its parent with v > tau_k}; the root is the node of level 0.  A node C
+ *   of level k >= 1 is significant iff sum_C (v - tau_k) > deblend_cont *
+ *   F_root, F_root = sum_root v, all in float64 (operands converted first, sums
+ *   in any order).  Only children of significant nodes are examined.  The
+ *   root's objects are the leaves: significant nodes without a significant
+ *   child.  A chain gives one object, the whole root; n = 1 does not deblend.
+ *   At most ceil(H/2) * ceil(W/2) objects per problem (leaves are pairwise
+ *   non-adjacent).
+ * Gather (roots with two or more leaves): leaves are numbered by their
+ *   smallest flat pixel index i*W + j; in synchronous sweeps every unassigned
+ *   root pixel with an assigned 8-neighbour takes the label of the neighbour
+ *   with the largest v (ties: the smaller number), until none is unassigned.
+ * Object statistics, float64, pixel (i, j) at (i + 0.5, j + 0.5): F = sum v,
+ *   npix, hbar = sum v h / F, wbar likewise; hh, ww, hw the v-weighted means of
+ *   squares minus the squares of means; if hh ww - hw^2 < 1/144 add 1/12 to hh
+ *   and ww; d = hh ww - hw^2; a^2 = (hh + ww)/2 + sqrt(((hh - ww)/2)^2 + hw^2);
+ *   c_hh = ww/d, c_ww = hh/d, c_hw = -2 hw/d; mthresh = (the minarea-th largest
+ *   v of the object) - tau, 0 when npix < minarea.
+ * Clean (only where clean_param[g] = beta > 0): objects in the order of
+ *   descending F (ties: the smaller smallest flat pixel index of the object);
+ *   from the second on, object i is absorbed by the first surviving earlier
+ *   object j with, U = 100 pi, amp = F_j / (2U), dh = hbar_i - hbar_j, dw alike:
+ *     dh^2 + dw^2 < 100 (a_i + a_j)^2,  amp > tau,
+ *     alpha = ((amp/tau)^(1/beta) - 1) U / npix_j,
+ *     val = 1 + alpha (c_hh,j dh^2 + c_ww,j dw^2 + c_hw,j dh dw),  1 < val < 1e10,
+ *     amp val^(-beta) > mthresh_i,
+ *   in float64, always with j's original statistics (absorbing updates
+ *   nothing); i's pixels take j's label.
+ * Outputs: F, hbar, wbar again over the survivors' final pixel sets; survivors
+ *   in the same order (descending F, ties to the smaller smallest pixel), the
+ *   first K kept; flux = F, loc = (hbar, wbar), each rounded to float32 once.
+ *   counts [T,G] int32 = min(found, K); locs [T,G,K,2], NaN past the count;
+ *   fluxes [T,G,K], 0 past the count: the est_* layout of
+ *   smcdet_match_catalogs with N = G.  Nullable: n_found [T,G] int32, the
+ *   survivors before the cap; segmap [T,G,H,W] int32, 0 or the 1-based rank of
+ *   the pixel's object in the output order (ranks above K included).
+ * One wavefront per problem, its working set in registers and a per-wave LDS
+ * slab; H*W <= 64 puts one pixel on each lane (four problems per workgroup),
+ * larger images stride the pixels over the lanes.  No atomics, no global
+ * scratch: the same bits on every run and for every grouping of the settings
+ * into launches.
+ * H*W > SMCDET_EXTRACT_MAX_PIXELS, K > SMCDET_MATCH_MAX_SOURCES,
+ * deblend_nthresh above 64 or not a power of two, T*G above 2^31-1:
+ * SMCDET_EUNSUPPORTED; a null required buffer or a size below 1:
+ * SMCDET_EINVAL.  Everything is checked before any device work. */
+int smcdet_extract(const float* images, const float* background, const float* sigma,
+                   int32_t T, int32_t H, int32_t W,
+                   const float* thresh, const int32_t* minarea, const float* deblend_cont,
+                   const float* clean_param, int32_t G, int32_t deblend_nthresh, int32_t K,
+                   int32_t* counts, float* locs, float* fluxes,
+                   int32_t* n_found, int32_t* segmap, void* stream);
+
 /* ---- tile aggregation (smcdet/aggregate.py:8-593, Aggregate) ------------- */
 #define SMCDET_AGG_MAX_SOURCES 4096
 

@@ -10,7 +10,9 @@ posterior mean / variance image and posterior-predictive checks of a run;
 `calibration` (the reference's results notebooks, by hand) gives count
 posteriors, interval coverage, quantile bands and bootstrap bands;
 `convergence` (not in the reference) gives split-R-hat, effective sample sizes
-and Monte Carlo standard errors of MCMC chains.
+and Monte Carlo standard errors of MCMC chains; `extract` (the scripts'
+run_sep.py baseline, without sep) is a classical multi-threshold source
+extractor with the grid search of its hyperparameters for F1.
 """
 import importlib
 import sys
@@ -20,7 +22,7 @@ from . import _hip  # noqa: F401
 __version__ = "0.1.0"
 
 _DROP_IN = ("sampler", "kernel", "images", "prior", "distributions", "aggregate",
-            "metrics", "condense", "predictive", "calibration", "convergence")
+            "metrics", "condense", "predictive", "calibration", "convergence", "extract")
 
 
 def install_as_smcdet():
