@@ -105,6 +105,12 @@ extern "C" {
  * 16x16 block whose Gaussian PSF terms come from a rank-4 MFMA); results
  * differ by float32 rounding of the profile */
 #define SMCDET_MH_NO_BLOCK 16384u
+/* diagnostic: M71 32x32 tiles with psf_radius 8 through the sweep that reads
+ * the tile geometry at run time (every other shape's kernel) instead of the
+ * instantiation with H, W and R compiled in; same results, bit for bit
+ * (DESIGN.md §4.1).  Added under SMCDET_ABI_VERSION 20 (additive: a flag bit
+ * that was free; no entry point or struct changed). */
+#define SMCDET_MH_GENERIC_GEOMETRY 32768u
 
 /* Image model (smcdet/images.py:6-26 ImageModel, :105-145 M71ImageModel). */
 typedef struct smcdet_image_model {

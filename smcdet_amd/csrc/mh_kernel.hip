@@ -89,6 +89,7 @@ struct MhArgs {
   int no_psf_cache;                  // SMCDET_MH_NO_PSF_CACHE (diagnostic)
   int no_rcp_cache;                  // SMCDET_MH_NO_RCP_CACHE (diagnostic)
   int blk_slots;                     // block form (M71, same anchor) from this many slots; 0: off
+  int generic_geometry;              // SMCDET_MH_GENERIC_GEOMETRY
   const float4* psf_tab;             // M71 radial PSF table [kTabNodes] (or null: exp2/log2)
   float tab_inv_h;                   // 1 / its node spacing in r^2
   const float* img;                  // [T,H,W]
@@ -441,6 +442,17 @@ constexpr int mh_waves_per_eu() {
 template <int PPL>
 constexpr int mh_slots() { return PPL == 1 ? 1 : kSlots; }
 
+// tile geometry of mh_sweep_kernel (GEO)
+struct GeoRun {
+  static constexpr bool kFixed = false;
+  static constexpr int kH = 0, kW = 0, kR = 0;
+};
+template <int H_, int W_, int R_>
+struct GeoFixed {
+  static constexpr bool kFixed = true;
+  static constexpr int kH = H_, kW = W_, kR = R_;
+};
+
 // TAIL: the fused SMC step's instantiation (a.has_tail); the sweep alone
 // compiles without the tail pass, which would otherwise raise its SGPR
 // pressure (spills reloaded by v_readlane in the loop).
@@ -457,10 +469,20 @@ constexpr int mh_slots() { return PPL == 1 ? 1 : kSlots; }
 // TB: M71 incremental sweeps with the radial PSF table (psf_tab, device.h)
 // staged into LDS after the images / caches: every union-window PSF value
 // (and the PSF cache's rows) comes from the table.
+// GEO: the tile geometry (H, W, psf radius R): GeoRun reads the model's values
+// at run time; GeoFixed<H, W, R> compiles them in (the host dispatches it only
+// for models with exactly these values), so the row stride is a shift, the
+// window clamps are literals and the block form's four rows pair up in
+// ds_read2 / ds_write2.  Integer addressing only: the LDS layout, every
+// floating-point operation and its order are GeoRun's, so results are
+// bit-identical.
 template <int MODEL, bool REPLAY, bool FULL, int PPL, bool PAIRED, bool TAIL, bool GL = false,
-          bool PC = false, bool RV = false, bool TB = false>
+          bool PC = false, bool RV = false, bool TB = false, class GEO = GeoRun>
 __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) void mh_sweep_kernel(
     MhArgs a) {
+  static_assert(!GEO::kFixed || (RV && PPL > 1 && GEO::kH * GEO::kW <= 64 * PPL &&
+                                 GEO::kH * GEO::kW > 16 * PPL),
+                "compiled-in geometry: the 1/v variant at its own PPL");
   static_assert(!PC || (PPL == 1 && !FULL && !GL && !TAIL), "PSF cache: small incremental tiles");
   static_assert(!RV || (MODEL == SMCDET_MODEL_M71 && PPL > 1 && !FULL && !GL && !TAIL && PAIRED),
                 "1/v cache: M71 register-render tiles, incremental, paired");
@@ -472,7 +494,16 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
   __shared__ int wg_acc, wg_done;  // last-iteration accepts / finished waves of this workgroup
   __shared__ int wg_last;          // this workgroup finished its tile last (fused tail)
   if (a.go && *a.go == 0) return;  // speculatively enqueued sweep that must not run
-  const DevModel& m = a.m;
+  // the model as the kernel body and the device helpers read it: a.m, or a
+  // copy whose H, W, R are GEO's literals
+  [[maybe_unused]] DevModel mgeo;
+  if constexpr (GEO::kFixed) {
+    mgeo = a.m;
+    mgeo.H = GEO::kH;
+    mgeo.W = GEO::kW;
+    mgeo.R = GEO::kR;
+  }
+  const DevModel& m = GEO::kFixed ? mgeo : a.m;
   [[maybe_unused]] const int trow = (int)(blockIdx.x * kMhWaves + (threadIdx.x >> 6));
   SMC_TRACE(trow, 0);
   SMC_WAVE_MARK(trow, 0);
@@ -597,9 +628,25 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
     cur_ll = pixel_sum<MODEL>(m, xs, lg, lam, nullptr, lane);
   }
   lam[HW + lane] = m.bg;
+  // a pixel row's offset (0 <= ph < 2^24).  Compiled-in W: a plain product, so
+  // a shift folded into the add; __umul24 of a literal keeps its 24-bit mask
+  // (v_lshlrev + v_and where the run-time form is one v_mad_u32_u24).
+  auto row_off = [&](int ph) -> int {
+    if constexpr (GEO::kFixed) return ph * GEO::kW;
+    else return (int)__umul24((unsigned)ph, (unsigned)m.W);
+  };
   [[maybe_unused]] float* rv = nullptr;
+  // rv as the packed union-window slots read it (position_delta2): with a
+  // literal H*W, rv[p] is lam[p] at a fixed 64-dword stride and the two loads
+  // of a pixel merge into one ds_read2st64_b32, whose register pair is (rate,
+  // 1/v) of ONE pixel where the packed arithmetic wants the rates of TWO --
+  // three v_mov per pair of pixels.  The offset from the run-time H*W keeps
+  // these loads single; the stores (finish) and the scalar forms, which a
+  // merged access serves as it is, use rv.
+  [[maybe_unused]] const float* rv_rd = nullptr;
   if constexpr (RV) {
     rv = lam + kMhWaves * HWp;
+    rv_rd = GEO::kFixed ? lam + kMhWaves * (a.m.H * a.m.W + kWave) : rv;
     wave_sync();
     if constexpr (PPL > 0) {
       // (PPL + 1) cells per lane: the LDS reads first, then the reciprocals
@@ -856,7 +903,7 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
           const int aa = (int)(__umul24((unsigned)q, magic) >> 16);
           const int bb = q - (int)__umul24((unsigned)aa, (unsigned)bw);
           const int ph = r0 + aa, pw = c0 + bb;
-          const int p = valid ? (int)__umul24((unsigned)ph, (unsigned)m.W) + pw : HW + lane;
+          const int p = valid ? row_off(ph) + pw : HW + lane;
           float lnew, rnew, e;
           if constexpr (PC)
             e = position_delta_pc<MODEL, win, TB>(m, xs, lg, lam, pcw + P.j * HW, tab, tinv, p,
@@ -892,13 +939,13 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
             aa[h] = (int)(__umul24((unsigned)q, magic) >> 16);
             bb[h] = q - (int)__umul24((unsigned)aa[h], (unsigned)bw);
             const int ph = r0 + aa[h], pw = c0 + bb[h];
-            p[h] = valid[h] ? (int)__umul24((unsigned)ph, (unsigned)m.W) + pw : HW + lane;
+            p[h] = valid[h] ? row_off(ph) + pw : HW + lane;
             fph[h] = (float)ph + 0.5f;
             fpw[h] = (float)pw + 0.5f;
           }
           f2 lnew, rnew;
-          f2 e = position_delta2<MODEL, win, GL, RV, TB>(m, xs, lg, lam, rv, tab, tinv, p, aa, bb,
-                                                         fph, fpw, P, amp_o, amp_n, ao_h, ao_w,
+          f2 e = position_delta2<MODEL, win, GL, RV, TB>(m, xs, lg, lam, rv_rd, tab, tinv, p, aa,
+                                                         bb, fph, fpw, P, amp_o, amp_n, ao_h, ao_w,
                                                          an_h, an_w, lnew, rnew);
           e.x = valid[0] ? e.x : 0.f;
           e.y = valid[1] ? e.y : 0.f;
@@ -919,7 +966,7 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
           const int aa = (int)(__umul24((unsigned)q, magic) >> 16);
           const int bb = q - (int)__umul24((unsigned)aa, (unsigned)bw);
           const int ph = r0 + aa, pw = c0 + bb;
-          const int p = valid ? (int)__umul24((unsigned)ph, (unsigned)m.W) + pw : HW + lane;
+          const int p = valid ? row_off(ph) + pw : HW + lane;
           float lnew, rnew;
           const float e = position_delta<MODEL, win, GL, RV, TB>(m, xs, lg, lam, rv, tab, tinv, p,
                                                              aa, bb, ph, pw, P, amp_o, amp_n,
@@ -952,7 +999,7 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
           const int aa = (int)(((float)q + 0.5f) * inv_bw);
           const int bb = q - (int)__umul24((unsigned)aa, (unsigned)bw);
           const int ph = r0 + aa, pw = c0 + bb;
-          const int p = (int)__umul24((unsigned)ph, (unsigned)m.W) + pw;
+          const int p = row_off(ph) + pw;
           float lnew, rnew;
           acc += position_delta<MODEL, true, GL, RV, TB>(m, xs, lg, lam, rv, tab, tinv, p, aa, bb,
                                                          ph, pw, P, amp_o, amp_n, ao_h, ao_w, an_h,
@@ -1321,9 +1368,16 @@ static int launch_mh1(const MhArgs& a, dim3 grid, size_t lds, hipStream_t st) {
         return go_variant(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, false,
                                           false, true>, with_tab(lds));
     }
-    if (rv && fits(lds_rv, 4))
+    if (rv && fits(lds_rv, 4)) {
+      // the headline geometry (32x32 tiles, R = 8) compiled in; same LDS bytes
+      if constexpr (PPL == 16) {
+        if (a.m.H == 32 && a.m.W == 32 && a.m.R == 8 && !a.generic_geometry)
+          return go_variant(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, false,
+                                            true, false, GeoFixed<32, 32, 8>>, lds_rv);
+      }
       return go_variant(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, false, true>,
                         lds_rv);
+    }
     if constexpr (!kDiag) {
       if (!tail) return set_error(SMCDET_EUNSUPPORTED, "M71 sweep: the 1/v image does not fit");
     }
@@ -1573,6 +1627,15 @@ static int mh_sweep_impl(const smcdet_image_model_t* model, const smcdet_prior_t
   rc = validate_prior(prior);
   if (rc) return rc;
   if (!mh) return set_error(SMCDET_EINVAL, "mh params are null");
+  // (before the buffers are looked at: which flags a build takes -- the other
+  // diagnostic ones, SMCDET_MH_NO_PSF_CACHE / _NO_BLOCK / _GENERIC_GEOMETRY, run
+  // in the product too -- shows without a device)
+  if (!kDiag && (flags & (SMCDET_MH_ABLATE_LIKELIHOOD | SMCDET_MH_ABLATE_PROPOSAL |
+                          SMCDET_MH_SCALAR_SLOTS | SMCDET_MH_PSF_TABLE | SMCDET_MH_NO_RCP_CACHE)))
+    return set_error(SMCDET_EUNSUPPORTED,
+                     "MH flags 0x%x: diagnostic variants (ablations, scalar slots, PSF table, no "
+                     "1/v cache) are in the diagnostic build only (make diag -> "
+                     "libsmcdet_hip_diag.so)", flags);
   const bool global_tile = model->H * model->W > kMaxLdsPixels;
   if (global_tile && !rate_out)
     return set_error(SMCDET_EINVAL,
@@ -1717,18 +1780,13 @@ static int mh_sweep_impl(const smcdet_image_model_t* model, const smcdet_prior_t
     }
   }
   const bool full = (flags & SMCDET_MH_FULL_RECOMPUTE) != 0;
-  if (!kDiag && (flags & (SMCDET_MH_ABLATE_LIKELIHOOD | SMCDET_MH_ABLATE_PROPOSAL |
-                          SMCDET_MH_SCALAR_SLOTS | SMCDET_MH_PSF_TABLE | SMCDET_MH_NO_RCP_CACHE)))
-    return set_error(SMCDET_EUNSUPPORTED,
-                     "MH flags 0x%x: diagnostic variants (ablations, scalar slots, PSF table, no "
-                     "1/v cache) are in the diagnostic build only (make diag -> "
-                     "libsmcdet_hip_diag.so)", flags);
   a.ablate = flags & (SMCDET_MH_ABLATE_LIKELIHOOD | SMCDET_MH_ABLATE_PROPOSAL);
   a.by_count = (flags & SMCDET_MH_COMPONENT_BY_COUNT) != 0;
   a.scalar_slots = (flags & SMCDET_MH_SCALAR_SLOTS) != 0;
   a.skip_done = (flags & SMCDET_MH_SKIP_DONE) != 0;
   a.no_psf_cache = (flags & SMCDET_MH_NO_PSF_CACHE) != 0;
   a.no_rcp_cache = (flags & SMCDET_MH_NO_RCP_CACHE) != 0;
+  a.generic_geometry = (flags & SMCDET_MH_GENERIC_GEOMETRY) != 0;
   // the block form for same-anchor M71 steps whose union window takes at least
   // this many 64-pixel slots (SMCDET_MH_BLOCK_SLOTS overrides, for A/Bs)
   a.blk_slots = (flags & SMCDET_MH_NO_BLOCK) ? 0 : 5;
