@@ -111,6 +111,12 @@ extern "C" {
  * (DESIGN.md §4.1).  Added under SMCDET_ABI_VERSION 20 (additive: a flag bit
  * that was free; no entry point or struct changed). */
 #define SMCDET_MH_GENERIC_GEOMETRY 32768u
+/* diagnostic: the sweep's rate images stored with plain stores where it would
+ * store them write-through (launches of one resident round of workgroups: the
+ * dirty lines then wait in the L2 for the write-back at the kernel's end);
+ * same results, bit for bit.  Additive: a flag bit that was
+ * free; no entry point or struct changed. */
+#define SMCDET_MH_NO_WRITE_THROUGH 65536u
 
 /* Image model (smcdet/images.py:6-26 ImageModel, :105-145 M71ImageModel). */
 typedef struct smcdet_image_model {

@@ -26,6 +26,7 @@ SMCDET_MH_FULL_RECOMPUTE = 1
 SMCDET_MH_COMPONENT_BY_COUNT = 2
 SMCDET_MH_SKIP_DONE = 4
 SMCDET_MH_GENERIC_GEOMETRY = 32768  # diagnostic: 32x32 / R = 8 tiles through the run-time-geometry sweep
+SMCDET_MH_NO_WRITE_THROUGH = 65536  # diagnostic: plain rate-image stores where the sweep stores write-through
 ABI_VERSION = 20
 SMCDET_SMC_FREEZE_DONE = 1
 SMCDET_SMC_TWO_LAUNCH = 2

@@ -4,6 +4,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <atomic>
+
 #include "device.h"
 
 namespace smcdet {
@@ -33,6 +35,21 @@ int ensure_lds(const void* kernel, size_t bytes) {
           hipSuccess)
     return set_error(SMCDET_EHIP, "hipFuncSetAttribute(%zu B LDS) failed", bytes);
   return SMCDET_OK;
+}
+
+int device_cu_count() {
+  constexpr int kMaxDev = 64;
+  static std::atomic<int> cus[kMaxDev];  // 0: not asked yet
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return 0;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        n <= 0)
+      return 0;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
 }
 
 // ---- launch timing pool (smcdet_launch_timing / _read) ----------------------

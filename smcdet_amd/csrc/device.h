@@ -87,6 +87,9 @@ int set_error(int code, const char* fmt, ...);
 int check_launch(const char* what);
 // raises the kernel's dynamic-LDS limit when bytes > 64 KiB (<= 160 KiB)
 int ensure_lds(const void* kernel, size_t bytes);
+// compute units of the current device (asked once per device; 0 if the query
+// fails, so a policy that needs the count stays off)
+int device_cu_count();
 // launch timing (smcdet_launch_timing): the next start / stop event pair of
 // the pool, or false (nulls) when timing is off or the pool is used up
 bool timing_next(hipEvent_t* start, hipEvent_t* stop);
@@ -228,6 +231,28 @@ __device__ __forceinline__ int readlane(int v, int lane) {
 // tells the compiler what it cannot prove, so control flow on it is scalar
 __device__ __forceinline__ float wave_uniform(float v) {
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
+// a pointer every lane holds alike, as an SGPR pair
+template <class T>
+__device__ __forceinline__ T* wave_uniform_ptr(T* p) {
+  const uint64_t b = (uint64_t)p;
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32));
+  return (T*)(((uint64_t)hi << 32) | lo);
+}
+// Agent-scope write-through stores (cache policy sc1) of 16 bytes per lane:
+// the bytes go to memory as they are stored instead of staying dirty in the
+// L2 until the kernel's end, where the next launch waits for their write-back.
+// wt_buffer: the descriptor of `bytes` bytes at the wave-uniform `base`;
+// store_wt16 at a byte offset into it (a store past `bytes` is dropped).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wt_buffer(float* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(wave_uniform_ptr(base), 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ void store_wt16(__amdgpu_buffer_rsrc_t rsrc, int byte_off, float4 v) {
+  typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
+  const u4_t b = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z),
+                  __float_as_uint(v.w)};
+  __builtin_amdgcn_raw_buffer_store_b128(b, rsrc, byte_off, 0, /*sc1*/ 16);
 }
 // v with lane `lane` replaced by the wave-uniform x
 __device__ __forceinline__ float writelane(float x, int lane, float v) {
@@ -632,6 +657,31 @@ __device__ __forceinline__ void stage_image(const float* __restrict__ img, float
     const float x = img[p];
     xs[p] = x;
     if constexpr (MODEL == SMCDET_MODEL_POISSON) lg[p] = poisson_image_term(x);
+  }
+}
+// The same staging, four pixels per thread and pass with their loads all
+// issued before the first LDS store: a pass is one global round trip (a 32x32
+// tile staged by 256 threads: one instead of four).  The MH sweep's, where
+// every wave of the launch stages at the same time and nothing hides the trips.
+template <int MODEL>
+__device__ __forceinline__ void stage_image4(const float* __restrict__ img, float* xs, float* lg,
+                                             int HW, int tid, int nthreads) {
+  constexpr int kU = 4;
+  for (int p0 = tid; p0 < HW; p0 += kU * nthreads) {
+    float x[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int p = p0 + u * nthreads;
+      if (p < HW) x[u] = img[p];
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int p = p0 + u * nthreads;
+      if (p < HW) {
+        xs[p] = x[u];
+        if constexpr (MODEL == SMCDET_MODEL_POISSON) lg[p] = poisson_image_term(x[u]);
+      }
+    }
   }
 }
 

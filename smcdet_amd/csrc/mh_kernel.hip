@@ -90,6 +90,12 @@ struct MhArgs {
   int no_rcp_cache;                  // SMCDET_MH_NO_RCP_CACHE (diagnostic)
   int blk_slots;                     // block form (M71, same anchor) from this many slots; 0: off
   int generic_geometry;              // SMCDET_MH_GENERIC_GEOMETRY
+  int no_write_through;              // SMCDET_MH_NO_WRITE_THROUGH (diagnostic)
+  // rate_out stored write-through (wt_buffer, device.h): set by the host when
+  // the grid is one resident round of workgroups (launch_mh1) -- every wave's
+  // image is then dirty in the L2 at the kernel's end, and the next launch
+  // waits for the write-back; the epilogue alone reads it
+  int write_through;
   const float4* psf_tab;             // M71 radial PSF table [kTabNodes] (or null: exp2/log2)
   float tab_inv_h;                   // 1 / its node spacing in r^2
   const float* img;                  // [T,H,W]
@@ -357,46 +363,71 @@ __device__ __forceinline__ float position_delta_pc(const DevModel& m, const floa
 }
 
 // Persisted rate image in / out for tiles of <= 64*PPL pixels: each lane's
-// (at most ceil(PPL/4)) float4 pieces all issued before any is used.
+// (at most ceil(PPL/4)) float4 pieces all issued before any is used.  The
+// copy in is two calls, so the loads are in flight with the particle's other
+// loads before anything waits: rate_load_regs issues them into r (kRateRegs
+// floats: the float4 pieces, or one float per 64 pixels where H*W % 4 != 0),
+// rate_store_lds writes the LDS image from r -- and, with RV, the 1/v image
+// from the same registers (the operation of the kernel's 1/v fill on the same
+// values: the same bits, without reading the image back from LDS).
 template <int PPL>
-__device__ __forceinline__ void copy_in_regs(const float* __restrict__ rin, float* lam, int HW,
-                                             int lane) {
+constexpr int rate_regs() { return 4 * ((PPL + 3) / 4); }
+template <int PPL>
+__device__ __forceinline__ void rate_load_regs(const float* __restrict__ rin,
+                                               float (&r)[rate_regs<PPL>()], int HW, int lane) {
   constexpr int NV = (PPL + 3) / 4;
   if ((HW & 3) == 0) {
-    float4 v[NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      const int p = 4 * (k * kWave + lane);
-      if (p < HW) v[k] = *reinterpret_cast<const float4*>(rin + p);
-    }
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const int p = 4 * (k * kWave + lane);
       if (p < HW) {
-        lam[p] = v[k].x;
-        lam[p + 1] = v[k].y;
-        lam[p + 2] = v[k].z;
-        lam[p + 3] = v[k].w;
+        const float4 v = *reinterpret_cast<const float4*>(rin + p);
+        r[4 * k] = v.x;
+        r[4 * k + 1] = v.y;
+        r[4 * k + 2] = v.z;
+        r[4 * k + 3] = v.w;
       }
     }
   } else {
-    float v[PPL];
 #pragma unroll
     for (int k = 0; k < PPL; ++k) {
       const int p = k * kWave + lane;
-      if (p < HW) v[k] = rin[p];
-    }
-#pragma unroll
-    for (int k = 0; k < PPL; ++k) {
-      const int p = k * kWave + lane;
-      if (p < HW) lam[p] = v[k];
+      if (p < HW) r[k] = rin[p];
     }
   }
-  wave_sync();
 }
+template <int PPL, bool RV>
+__device__ __forceinline__ void rate_store_lds(const DevModel& m,
+                                               const float (&r)[rate_regs<PPL>()], float* lam,
+                                               [[maybe_unused]] float* rv, int HW, int lane) {
+  constexpr int NV = (PPL + 3) / 4;
+  if ((HW & 3) == 0) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      const int p = 4 * (k * kWave + lane);
+      if (p < HW) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          lam[p + c] = r[4 * k + c];
+          if constexpr (RV) rv[p + c] = fast_rcp(fmaf(m.eta, r[4 * k + c], m.s0sq));
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) {
+      const int p = k * kWave + lane;
+      if (p < HW) {
+        lam[p] = r[k];
+        if constexpr (RV) rv[p] = fast_rcp(fmaf(m.eta, r[k], m.s0sq));
+      }
+    }
+  }
+}
+// wt: write-through stores (MhArgs::write_through), wave-uniform
 template <int PPL>
 __device__ __forceinline__ void copy_out_regs(const float* lam, float* __restrict__ rout, int HW,
-                                              int lane) {
+                                              int lane, bool wt) {
   constexpr int NV = (PPL + 3) / 4;
   if ((HW & 3) == 0) {
     float4 v[NV];
@@ -405,10 +436,19 @@ __device__ __forceinline__ void copy_out_regs(const float* lam, float* __restric
       const int p = 4 * (k * kWave + lane);
       if (p < HW) v[k] = make_float4(lam[p], lam[p + 1], lam[p + 2], lam[p + 3]);
     }
+    if (wt) {
+      const __amdgpu_buffer_rsrc_t rs = wt_buffer(rout, HW * (int)sizeof(float));
 #pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      const int p = 4 * (k * kWave + lane);
-      if (p < HW) *reinterpret_cast<float4*>(rout + p) = v[k];
+      for (int k = 0; k < NV; ++k) {
+        const int p = 4 * (k * kWave + lane);
+        if (p < HW) store_wt16(rs, p * (int)sizeof(float), v[k]);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < NV; ++k) {
+        const int p = 4 * (k * kWave + lane);
+        if (p < HW) *reinterpret_cast<float4*>(rout + p) = v[k];
+      }
     }
   } else {
     for (int p = lane; p < HW; p += kWave) rout[p] = lam[p];
@@ -515,9 +555,37 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
   float* xs = smem;
   float* lg = smem + HWp;
   float* lam = smem + kImg * HWp + wave * HWp;
+  // kHT: the short head and tail of the register-render tiles above 64
+  // pixels (the headline's 32x32 and every 65..1024-pixel shape), whose
+  // launches are one resident round of waves all in the same phase.  The
+  // small-tile and LDS-render instantiations keep the plain order below: with
+  // the short one their loops allocate more registers (<= 64 px: 67 -> 70
+  // VGPRs, 61 -> 65 spilled SGPRs) and their many-round launches (C4, C5) ran
+  // 0.3-0.6 % slower.
+  constexpr bool kHT = PPL > 1;
+  // What the ancestor search and the loop bounds start from -- the bins'
+  // first level and offset U (or the ancestor index) and the temperature --
+  // is loaded ahead of the image staging: one global round trip with the
+  // image's instead of two more behind the barrier.
+  const int n = blockIdx.x * kMhWaves + wave;
+  const size_t pid = (size_t)t * a.N + n;
+  [[maybe_unused]] float tau_v = 0.f, anc_U = 0.f, anc_b = 0.f;
+  [[maybe_unused]] int64_t anc_i = 0;
+  if constexpr (kHT) {
+    tau_v = a.temperature[t];
+    if (a.anc_bins) {
+      anc_U = a.anc_bins[(size_t)a.T * a.N + t];
+      if (bins_coarse_lane(a.N))
+        anc_b = a.anc_bins[(size_t)a.T * (a.N + 1) + (size_t)t * kBinsCoarse + lane];
+    } else if (a.ancestors && n < a.N) {
+      anc_i = a.ancestors[pid];
+    }
+  }
   if constexpr (GL) {
     xs = const_cast<float*>(a.img) + (size_t)t * HW;
     lg = nullptr;
+  } else if constexpr (kHT) {
+    stage_image4<MODEL>(a.img + (size_t)t * HW, xs, lg, HW, threadIdx.x, kMhBlock);
   } else {
     stage_image<MODEL>(a.img + (size_t)t * HW, xs, lg, HW, threadIdx.x, kMhBlock);
   }
@@ -542,42 +610,70 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
   }
   __syncthreads();
   SMC_TRACE(trow, 1);
-  const int n = blockIdx.x * kMhWaves + wave;
   if (n >= a.N) return;  // (never with the fused tail: N % 4 == 0, host-checked)
 
   const int N = a.N, S = a.S;
-  const size_t pid = (size_t)t * N + n;
-  size_t src = a.ancestors ? (size_t)t * N + (size_t)a.ancestors[pid] : pid;
-  if (a.anc_bins)  // the wave finds its ancestor in the previous tile pass's bins
-    src = (size_t)t * N +
-          (size_t)bins_ancestor(a.anc_bins + (size_t)t * N,
-                                a.anc_bins + (size_t)a.T * (N + 1) + (size_t)t * kBinsCoarse, N,
-                                a.anc_bins[(size_t)a.T * N + t], n);
+  size_t src;
+  if constexpr (kHT) {
+    src = a.ancestors ? (size_t)t * N + (size_t)anc_i : pid;
+    if (a.anc_bins)  // the wave finds its ancestor in the previous tile pass's bins
+      src = (size_t)t * N +
+            (size_t)bins_ancestor_from(a.anc_bins + (size_t)t * N, true, anc_b, N, anc_U, n);
+  } else {
+    src = a.ancestors ? (size_t)t * N + (size_t)a.ancestors[pid] : pid;
+    if (a.anc_bins)
+      src = (size_t)t * N +
+            (size_t)bins_ancestor(a.anc_bins + (size_t)t * N,
+                                  a.anc_bins + (size_t)a.T * (N + 1) + (size_t)t * kBinsCoarse, N,
+                                  a.anc_bins[(size_t)a.T * N + t], n);
+  }
   if constexpr (GL) lam = a.rate_out + pid * (size_t)HWp;
+  // kHT: everything read at src -- count, state, persisted rate image -- is
+  // issued together, before the first wait on any of it (one round trip, not
+  // three); otherwise the count is waited for first and the state and the
+  // image are loaded where they are used.
+  float count_v = 0.f;
+  if constexpr (kHT) count_v = a.counts_in[src];
+  // ---- particle state: lane s holds source s --------------------------------
+  float sh = 0.f, sw = 0.f, sfx = 0.f;
+  auto load_state = [&]() {
+    if (lane < S) {
+      sh = a.locs_in[(src * S + lane) * 2 + 0];
+      sw = a.locs_in[(src * S + lane) * 2 + 1];
+      sfx = a.fluxes_in[src * S + lane];
+    }
+  };
+  // register-render tiles: the ancestor's rate image in registers (rate_load_regs)
+  [[maybe_unused]] float rate_r[rate_regs<(PPL > 0 ? PPL : 1)>()];
+  if constexpr (kHT) {
+    load_state();
+    if constexpr (!FULL && !GL) {
+      if (a.rate_in) rate_load_regs<PPL>(a.rate_in + src * (size_t)HW, rate_r, HW, lane);
+    }
+  } else {
+    count_v = a.counts_in[src];
+  }
   // One particle per wavefront: every lane loads the same count (src depends
   // on the wave, not the lane), which the compiler cannot prove.  Taken from
   // the first lane once, here, Sj, K and with them the whole iteration loop
   // (back edge, batch bounds, `dirty`) are scalar instead of an exec-mask
   // loop on VGPR copies of wave-uniform values.
-  const float count = wave_uniform(a.counts_in[src]);
+  const float count = wave_uniform(count_v);
   if (a.counts_out && lane == 0) a.counts_out[pid] = count;
   // range of the moved component: 0..S-1 (kernel.py:35-37), or 0..count-1
   // for count-stratified populations padded to S sources (count 0: no moves)
   const int Sj = a.by_count ? min(max((int)count, 0), S) : S;
-  const float tau = wave_uniform(a.temperature[t]);
+  if constexpr (!kHT) tau_v = a.temperature[t];
+  const float tau = wave_uniform(tau_v);
   // independent stopping: a tile already at temperature 1 keeps its
   // (resampled) particles unchanged (SMCDET_MH_SKIP_DONE)
   const int K = (Sj > 0 && !(a.skip_done && tau >= 1.0f)) ? a.K : 0;
-
-  // ---- particle state: lane s holds source s --------------------------------
-  float sh = 0.f, sw = 0.f, sfx = 0.f;
-  if (lane < S) {
-    sh = a.locs_in[(src * S + lane) * 2 + 0];
-    sw = a.locs_in[(src * S + lane) * 2 + 1];
-    sfx = a.fluxes_in[src * S + lane];
-  }
+  if constexpr (!kHT) load_state();
   SMC_TRACE(trow, 2);
 
+  // the per-wave 1/v image (RV), after the rate images
+  [[maybe_unused]] float* rv = nullptr;
+  if constexpr (RV) rv = lam + kMhWaves * HWp;
   double cur_ll = 0.0;  // tracked only in FULL mode (incremental mode works on deltas)
   if constexpr (GL && !FULL) {
     // the working image is rate_out's row: copy the ancestor's row in, or render
@@ -594,12 +690,19 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
   } else if constexpr (!FULL) {
     if (a.rate_in) {
       // the ancestor's rate image, persisted by the previous sweep: no render
-      const float* rin = a.rate_in + src * (size_t)HW;
+      [[maybe_unused]] const float* rin = a.rate_in + src * (size_t)HW;
       if constexpr (PPL > 0) {
-        // HW <= 64*PPL (register-render tiles): every lane's float4 loads in
-        // flight before the LDS stores (the generic loop below kept at most
-        // two in flight: one HBM round trip per pair on the sweep's start)
-        copy_in_regs<PPL>(rin, lam, HW, lane);
+        // HW <= 64*PPL (register-render tiles): every lane's float4 loads were
+        // issued with the state's (the generic loop below kept at most two in
+        // flight: one HBM round trip per pair on the sweep's start); with RV
+        // the 1/v image is written from the same registers
+        if constexpr (!kHT) {
+          rate_load_regs<PPL>(rin, rate_r, HW, lane);
+          rate_store_lds<PPL, false>(m, rate_r, lam, nullptr, HW, lane);
+          wave_sync();
+        } else {
+          rate_store_lds<PPL, RV>(m, rate_r, lam, rv, HW, lane);
+        }
       } else if ((HW & 3) == 0) {
         for (int p = 4 * lane; p < HW; p += 4 * kWave) {
           const float4 v = *reinterpret_cast<const float4*>(rin + p);
@@ -635,7 +738,6 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
     if constexpr (GEO::kFixed) return ph * GEO::kW;
     else return (int)__umul24((unsigned)ph, (unsigned)m.W);
   };
-  [[maybe_unused]] float* rv = nullptr;
   // rv as the packed union-window slots read it (position_delta2): with a
   // literal H*W, rv[p] is lam[p] at a fixed 64-dword stride and the two loads
   // of a pixel merge into one ds_read2st64_b32, whose register pair is (rate,
@@ -645,10 +747,13 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
   // merged access serves as it is, use rv.
   [[maybe_unused]] const float* rv_rd = nullptr;
   if constexpr (RV) {
-    rv = lam + kMhWaves * HWp;
     rv_rd = GEO::kFixed ? lam + kMhWaves * (a.m.H * a.m.W + kWave) : rv;
     wave_sync();
-    if constexpr (PPL > 0) {
+    if (kHT && a.rate_in) {
+      // rate_store_lds wrote the pixels' 1/v beside their rates: the dummy
+      // cells' (the rate m.bg stored above) remain
+      rv[HW + lane] = fast_rcp(fmaf(m.eta, m.bg, m.s0sq));
+    } else if constexpr (PPL > 0) {
       // (PPL + 1) cells per lane: the LDS reads first, then the reciprocals
       constexpr int NR = PPL + 1;
       float v[NR];
@@ -1214,6 +1319,37 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
     a.locs_out[(pid * S + lane) * 2 + 1] = sw;
     a.fluxes_out[pid * S + lane] = sfx;
   }
+  // kHT: the rate image goes out first (LDS -> registers -> global), so its
+  // stores drain under the log-likelihood sum's arithmetic; write-through
+  // where the host asks for it (a.write_through), so they are in memory at
+  // the kernel's end.  Otherwise: after the sum, plain.
+  auto store_rate = [&]() {
+    if constexpr (!FULL && !GL) {  // (GL: the sweep worked in rate_out's row)
+      if (a.rate_out) {
+        float* rout = a.rate_out + pid * (size_t)HW;
+        if constexpr (kHT) {
+          // the flag is read only here: through the opaque pointer its kernarg
+          // load cannot be hoisted above the sweep, where it would stay live
+          // in an SGPR across the MH loop (as the fused tail reads its arguments)
+          const char* kp = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
+          __asm__ volatile("" : "+s"(kp));
+          const bool wt =
+              *reinterpret_cast<const int*>(kp + offsetof(MhArgs, write_through)) != 0;
+          wave_sync();
+          copy_out_regs<PPL>(lam, rout, HW, lane, wt);
+        } else if constexpr (PPL > 0) {
+          copy_out_regs<PPL>(lam, rout, HW, lane, false);
+        } else if ((HW & 3) == 0) {
+          for (int p = 4 * lane; p < HW; p += 4 * kWave)
+            *reinterpret_cast<float4*>(rout + p) = make_float4(lam[p], lam[p + 1], lam[p + 2],
+                                                               lam[p + 3]);
+        } else {
+          for (int p = lane; p < HW; p += kWave) rout[p] = lam[p];
+        }
+      }
+    }
+  };
+  if constexpr (kHT) store_rate();
   if (a.loglik_out) {
     double ll;
     if constexpr (!FULL) {
@@ -1230,20 +1366,7 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
     }
     if (lane == 0) a.loglik_out[pid] = (float)ll;
   }
-  if constexpr (!FULL && !GL) {  // (GL: the sweep worked in rate_out's row)
-    if (a.rate_out) {
-      float* rout = a.rate_out + pid * (size_t)HW;
-      if constexpr (PPL > 0) {
-        copy_out_regs<PPL>(lam, rout, HW, lane);
-      } else if ((HW & 3) == 0) {
-        for (int p = 4 * lane; p < HW; p += 4 * kWave)
-          *reinterpret_cast<float4*>(rout + p) = make_float4(lam[p], lam[p + 1], lam[p + 2],
-                                                             lam[p + 3]);
-      } else {
-        for (int p = lane; p < HW; p += kWave) rout[p] = lam[p];
-      }
-    }
-  }
+  if constexpr (!kHT) store_rate();
   SMC_TRACE(trow, 5);
   SMC_WAVE_MARK(trow, 1);
   // ---- acceptance rate of the last iteration (kernel.py:130), no extra launch:
@@ -1308,15 +1431,27 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
 }
 
 template <int MODEL, bool REPLAY, bool FULL, int PPL>
-static int launch_mh1(const MhArgs& a, dim3 grid, size_t lds, hipStream_t st) {
+static int launch_mh1(const MhArgs& a_in, dim3 grid, size_t lds, hipStream_t st) {
   // FULL mode never evaluates union-window slots: one instantiation
   constexpr bool kPair = !FULL;
   // (scalar slots: diagnostic build only, host-checked)
-  const bool paired = kPair && !(kDiag && a.scalar_slots);
+  const bool paired = kPair && !(kDiag && a_in.scalar_slots);
   // the fused tail exists only where tail_fusable() allows it
   constexpr bool kTail = !FULL && PPL != 1;
-  const bool tail = kTail && paired && a.has_tail;
-  if (a.has_tail && !tail) return set_error(SMCDET_EINVAL, "fused step: unsupported shape");
+  const bool tail = kTail && paired && a_in.has_tail;
+  if (a_in.has_tail && !tail) return set_error(SMCDET_EINVAL, "fused step: unsupported shape");
+  // Write-through rate-image stores (the register-render tiles above 64
+  // pixels: kHT in the kernel) where every workgroup is resident at once
+  // (one workgroup per SIMD row: the instantiation's waves per SIMD are its
+  // workgroups per CU): all the images are then still dirty in the L2 when
+  // the kernel ends.  A launch of several rounds has written the earlier
+  // rounds' back by then, and keeps the plain stores it was measured with;
+  // the fused tail keeps its stores and fences as they are.
+  MhArgs a = a_in;
+  a.write_through =
+      PPL > 1 && !FULL && !tail && a.rate_out != nullptr && !a.no_write_through &&
+      (long long)grid.x * grid.y <=
+          (long long)device_cu_count() * mh_waves_per_eu<PPL, REPLAY, FULL>();
   // The LDS-cached variants, richest first, where their workgroups per CU
   // (the occupancy the instantiation is built for) still fit the 160 KiB:
   // PC (small tiles) = the per-wave PSF cache, RV (M71, 65..1024 px) = the
@@ -1787,6 +1922,7 @@ static int mh_sweep_impl(const smcdet_image_model_t* model, const smcdet_prior_t
   a.no_psf_cache = (flags & SMCDET_MH_NO_PSF_CACHE) != 0;
   a.no_rcp_cache = (flags & SMCDET_MH_NO_RCP_CACHE) != 0;
   a.generic_geometry = (flags & SMCDET_MH_GENERIC_GEOMETRY) != 0;
+  a.no_write_through = (flags & SMCDET_MH_NO_WRITE_THROUGH) != 0;
   // the block form for same-anchor M71 steps whose union window takes at least
   // this many 64-pixel slots (SMCDET_MH_BLOCK_SLOTS overrides, for A/Bs)
   a.blk_slots = (flags & SMCDET_MH_NO_BLOCK) ? 0 : 5;

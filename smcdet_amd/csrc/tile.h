@@ -78,23 +78,28 @@ int launch_tile(const TileArgs& a, hipStream_t st);
 // pass's search would write.  Call from converged code; the result is
 // wave-uniform.
 constexpr int kBinsCoarse = 64;
-__device__ __forceinline__ int bins_ancestor(const float* __restrict__ bins,
-                                             const float* __restrict__ coarse, int N, float U,
-                                             int n) {
+// the lanes whose first-level chunk exists (the only ones that read `coarse`)
+__device__ __forceinline__ bool bins_coarse_lane(int N) {
+  return (int)(threadIdx.x & 63) * ((N + 63) >> 6) < N;
+}
+// bins_ancestor with the first level's value already in a register: coarse_b =
+// coarse[lane] in the lanes of bins_coarse_lane(N), loaded by the caller ahead
+// of other waits (`first` false: no coarse level, as with a null `coarse`)
+__device__ __forceinline__ int bins_ancestor_from(const float* __restrict__ bins, bool first,
+                                                  float coarse_b, int N, float U, int n) {
   const int lane = threadIdx.x & 63;
   const float Nf = (float)N;
   const bool pow2 = (N & (N - 1)) == 0;
   const float nu = (float)n + U;
   const float key = pow2 ? nu : nu / Nf;
   int lo = 0, len = N;
-  bool first = coarse != nullptr;
   while (true) {
     // chunk l = [l*step, min((l+1)*step, len)) of [lo, lo+len): its last bin
     // below the key means the whole chunk is (bins are monotone)
     const int step = (len + 63) >> 6;
     const bool valid = lane * step < len;
     const float b = !valid ? 0.f
-                  : first ? coarse[lane]
+                  : first ? coarse_b
                           : bins[lo + min((lane + 1) * step, len) - 1];
     first = false;
     const bool less = valid && (pow2 ? (b * Nf < key) : (b < key));
@@ -104,6 +109,12 @@ __device__ __forceinline__ int bins_ancestor(const float* __restrict__ bins,
     lo += c * step;
     len = min(step, len - c * step);
   }
+}
+__device__ __forceinline__ int bins_ancestor(const float* __restrict__ bins,
+                                             const float* __restrict__ coarse, int N, float U,
+                                             int n) {
+  const float b = (coarse != nullptr && bins_coarse_lane(N)) ? coarse[threadIdx.x & 63] : 0.f;
+  return bins_ancestor_from(bins, coarse != nullptr, b, N, U, n);
 }
 
 // the chunk-end index of coarse entry l: min((l+1)*c, N) - 1, c = ceil(N/64)
