@@ -4,7 +4,7 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result
 CSRC := smcdet_amd/csrc
 SRCS := $(CSRC)/common.hip $(CSRC)/model_kernels.hip $(CSRC)/mh_kernel.hip $(CSRC)/mala_kernel.hip $(CSRC)/chain_kernel.hip $(CSRC)/smc_kernels.hip $(CSRC)/agg_kernel.hip $(CSRC)/match_kernel.hip $(CSRC)/condense_kernel.hip $(CSRC)/predictive_kernel.hip $(CSRC)/summary_kernel.hip $(CSRC)/convergence_kernel.hip $(CSRC)/extract_kernel.hip
-HDRS := $(CSRC)/device.h $(CSRC)/render.h $(CSRC)/mcmc.h $(CSRC)/tile.h include/smcdet_hip.h
+HDRS := $(CSRC)/device.h $(CSRC)/render.h $(CSRC)/mcmc.h $(CSRC)/tile.h $(CSRC)/mh_plan.h include/smcdet_hip.h
 OBJS := $(SRCS:.hip=.o)
 LIB := smcdet_amd/libsmcdet_hip.so
 DIAG_DIR := build/diag
@@ -72,7 +72,7 @@ ASAN_OBJS := $(patsubst $(CSRC)/%.hip,$(ASAN_DIR)/%.o,$(SRCS))
 $(ASAN_DIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	mkdir -p $(ASAN_DIR)
 	$(ASAN_HIP) -c $< -o $@
-$(ASAN_DIR)/capi_driver.o: scripts/asan/capi_driver.cpp include/smcdet_hip.h
+$(ASAN_DIR)/capi_driver.o: scripts/asan/capi_driver.cpp $(CSRC)/mh_plan.h include/smcdet_hip.h
 	mkdir -p $(ASAN_DIR)
 	$(ASAN_HIP) -c $< -o $@
 $(ASAN_DIR)/capi_driver: $(ASAN_DIR)/capi_driver.o $(ASAN_OBJS)

@@ -4,11 +4,13 @@
 // tests/test_sanitizers.py without a GPU.  Every entry point is called with
 // the argument errors its validation must reject (null buffers, empty or
 // oversized shapes, unknown enums, inconsistent flags) and must return the
-// documented negative code with a message, touching no device memory.
+// documented negative code with a message, touching no device memory.  The MH
+// sweep's launch plan (a pure host function) is checked here too, row by row.
 #include <cstdio>
 #include <cstring>
 
 #include "../../include/smcdet_hip.h"
+#include "../../smcdet_amd/csrc/mh_plan.h"
 
 static int fails = 0;
 #define EXPECT(expr, code)                                                         \
@@ -23,6 +25,138 @@ static int fails = 0;
       ++fails;                                                                     \
     }                                                                              \
   } while (0)
+
+// The MH sweep's launch plan (smcdet_amd/csrc/mh_plan.h) row by row: which
+// instantiation, LDS bytes, tail and store policy each shape gets.  Every
+// variant computes the same bits, so only this table sees a wrong choice.
+// Unless a row says otherwise: CU count 256, rate_out present, T = 1; the
+// base LDS is (images + 4) (H W + 64) 4 B.  fused: smcdet_mh_sweep_step_fused's
+// answer (-1: not asked).
+namespace {
+using namespace smcdet;
+struct PlanRow {
+  const char* name;
+  int model, H, W, R, N, S, T;
+  uint32_t flags;
+  bool tail, two_launch, rate_out, diag, psf_tab;
+  MhVariant variant;
+  bool geo_fixed;
+  int ppl;
+  size_t lds;
+  MhTailMode tail_mode;
+  bool write_through;
+  int fused;
+};
+constexpr int M = SMCDET_MODEL_M71, P = SMCDET_MODEL_POISSON;
+constexpr uint32_t kGen = SMCDET_MH_GENERIC_GEOMETRY, kFull = SMCDET_MH_FULL_RECOMPUTE,
+                   kNoWt = SMCDET_MH_NO_WRITE_THROUGH, kNoPc = SMCDET_MH_NO_PSF_CACHE;
+constexpr bool T_ = true, F_ = false;
+const PlanRow kPlanRows[] = {
+    // name, model H W R N S T, flags, tail two rate_out diag tab -> variant geo ppl lds tail wt fused
+    {"c2", M, 32, 32, 8, 4096, 10, 1, 0, F_, F_, T_, F_, F_, kMhRV, T_, 16, 39168, kMhNoTail, T_, -1},
+    {"c2 generic geometry", M, 32, 32, 8, 4096, 10, 1, kGen, F_, F_, T_, F_, F_, kMhRV, F_, 16, 39168,
+     kMhNoTail, T_, -1},
+    {"c2 N=4100", M, 32, 32, 8, 4100, 10, 1, 0, F_, F_, T_, F_, F_, kMhRV, T_, 16, 39168, kMhNoTail,
+     F_, -1},
+    {"c2 T=2", M, 32, 32, 8, 4096, 10, 2, 0, F_, F_, T_, F_, F_, kMhRV, T_, 16, 39168, kMhNoTail, F_,
+     -1},
+    {"c2 no rate_out", M, 32, 32, 8, 4096, 10, 1, 0, F_, F_, F_, F_, F_, kMhRV, T_, 16, 39168,
+     kMhNoTail, F_, -1},
+    {"c2 no write-through", M, 32, 32, 8, 4096, 10, 1, kNoWt, F_, F_, T_, F_, F_, kMhRV, T_, 16,
+     39168, kMhNoTail, F_, -1},
+    {"c2 tail", M, 32, 32, 8, 4096, 10, 1, 0, T_, F_, T_, F_, F_, kMhTail, F_, 16, 32772,
+     kMhTailFused, F_, 1},
+    {"c2 tail two-launch", M, 32, 32, 8, 4096, 10, 1, 0, T_, T_, T_, F_, F_, kMhRV, T_, 16, 39168,
+     kMhTailSplit, T_, -1},
+    {"c2 tail N=4094", M, 32, 32, 8, 4094, 10, 1, 0, T_, F_, T_, F_, F_, kMhRV, T_, 16, 39168,
+     kMhTailSplit, T_, 0},
+    {"c2 tail N=4100", M, 32, 32, 8, 4100, 10, 1, 0, T_, F_, T_, F_, F_, kMhRV, T_, 16, 39168,
+     kMhTailSplit, F_, -1},
+    {"32x32 R=6", M, 32, 32, 6, 4096, 10, 1, 0, F_, F_, T_, F_, F_, kMhRV, F_, 16, 39168, kMhNoTail,
+     T_, -1},
+    {"24x40", M, 24, 40, 8, 4096, 10, 1, 0, F_, F_, T_, F_, F_, kMhRV, F_, 16, 9 * 1024 * 4,
+     kMhNoTail, T_, -1},
+    {"16x16", M, 16, 16, 8, 4096, 10, 1, 0, F_, F_, T_, F_, F_, kMhRV, F_, 4, 11520, kMhNoTail, T_,
+     -1},
+    {"c2 full", M, 32, 32, 8, 4096, 10, 1, kFull, F_, F_, T_, F_, F_, kMhUnpaired, F_, 16, 21760,
+     kMhNoTail, F_, -1},
+    {"c2 full tail", M, 32, 32, 8, 4096, 10, 1, kFull, T_, F_, T_, F_, F_, kMhUnpaired, F_, 16, 21760,
+     kMhTailSplit, F_, 0},
+    {"8x8", M, 8, 8, 8, 4096, 10, 1, 0, F_, F_, T_, F_, F_, kMhPC, F_, 1, 12800, kMhNoTail, F_, -1},
+    {"8x8 tail", M, 8, 8, 8, 4096, 10, 1, 0, T_, F_, T_, F_, F_, kMhPC, F_, 1, 12800, kMhTailSplit,
+     F_, 0},
+    {"8x8 S=19", M, 8, 8, 8, 4096, 19, 1, 0, F_, F_, T_, F_, F_, kMhPC, F_, 1, 22016, kMhNoTail, F_,
+     -1},
+    {"8x8 S=20", M, 8, 8, 8, 4096, 20, 1, 0, F_, F_, T_, F_, F_, kMhPaired, F_, 1, 2560, kMhNoTail,
+     F_, -1},  // 7 (23 040 + 1024) > 160 KiB
+    {"8x8 no PSF cache", M, 8, 8, 8, 4096, 10, 1, kNoPc, F_, F_, T_, F_, F_, kMhPaired, F_, 1, 2560,
+     kMhNoTail, F_, -1},
+    {"8x8 full", M, 8, 8, 8, 4096, 10, 1, kFull, F_, F_, T_, F_, F_, kMhUnpaired, F_, 1, 2560,
+     kMhNoTail, F_, -1},
+    {"poisson 8x8", P, 8, 8, 8, 4096, 10, 1, 0, F_, F_, T_, F_, F_, kMhPC, F_, 1, 13312, kMhNoTail,
+     F_, -1},
+    {"poisson 16x16 N=64", P, 16, 16, 8, 64, 10, 1, 0, F_, F_, T_, F_, F_, kMhPaired, F_, 4, 7680,
+     kMhNoTail, T_, -1},
+    {"64x64", M, 64, 64, 8, 4096, 10, 1, 0, F_, F_, T_, F_, F_, kMhPaired, F_, 0, 83200, kMhNoTail,
+     F_, -1},
+    {"64x64 tail", M, 64, 64, 8, 4096, 10, 1, 0, T_, F_, T_, F_, F_, kMhPaired, F_, 0, 83200,
+     kMhTailSplit, F_, 0},  // 4 (83 200 + 2048) > 160 KiB
+    {"128x128", M, 128, 128, 8, 4096, 10, 1, 0, F_, F_, T_, F_, F_, kMhGL, F_, 0, 0, kMhNoTail, F_,
+     -1},
+    {"128x128 tail", M, 128, 128, 8, 4096, 10, 1, 0, T_, F_, T_, F_, F_, kMhGL, F_, 0, 0,
+     kMhTailSplit, F_, 0},
+    // the diagnostic build's variants (the table: 513 float4 behind 16-B alignment)
+    {"diag c2 scalar slots", M, 32, 32, 8, 4096, 10, 1, SMCDET_MH_SCALAR_SLOTS, F_, F_, T_, T_, F_,
+     kMhUnpaired, F_, 16, 21760, kMhNoTail, T_, -1},
+    {"diag c2 no 1/v", M, 32, 32, 8, 4096, 10, 1, SMCDET_MH_NO_RCP_CACHE, F_, F_, T_, T_, F_,
+     kMhPaired, F_, 16, 21760, kMhNoTail, T_, -1},
+    {"diag c2 table", M, 32, 32, 8, 4096, 10, 1, SMCDET_MH_PSF_TABLE, F_, F_, T_, T_, T_, kMhTB, F_,
+     16, 21760 + 8208, kMhNoTail, T_, -1},  // with the 1/v image: 4 (47 376 + 1024) > 160 KiB
+    {"diag 16x16 table", M, 16, 16, 8, 4096, 10, 1, SMCDET_MH_PSF_TABLE, F_, F_, T_, T_, T_, kMhRVTB,
+     F_, 4, 11520 + 8208, kMhNoTail, T_, -1},
+    {"diag 8x8 table", M, 8, 8, 8, 4096, 10, 1, SMCDET_MH_PSF_TABLE, F_, F_, T_, T_, T_, kMhPCTB, F_,
+     1, 12800 + 8208, kMhNoTail, F_, -1},
+};
+
+int plan_table(const smcdet_image_model_t& base) {
+  int bad = 0;
+  for (const PlanRow& r : kPlanRows) {
+    MhPlanIn in{};
+    in.model = r.model, in.H = r.H, in.W = r.W, in.R = r.R, in.N = r.N, in.S = r.S, in.T = r.T;
+    in.flags = r.flags, in.tail = r.tail, in.two_launch = r.two_launch;
+    in.tail_lds = (size_t)(2 * r.N + 1) * 4;
+    in.rate_out = r.rate_out, in.psf_tab = r.psf_tab, in.cu_count = 256, in.diag = r.diag;
+    const MhPlan p = mh_plan(in);
+    if (p.status != SMCDET_OK || p.variant != r.variant || p.geo_fixed != r.geo_fixed ||
+        p.ppl != r.ppl || p.lds != r.lds || p.tail != r.tail_mode ||
+        p.write_through != r.write_through) {
+      std::printf("FAIL plan %s: status %d (%s) variant %d geo %d ppl %d lds %zu tail %d wt %d\n",
+                  r.name, p.status, p.msg, (int)p.variant, (int)p.geo_fixed, p.ppl, p.lds,
+                  (int)p.tail, (int)p.write_through);
+      ++bad;
+    }
+    if (r.fused >= 0) {
+      smcdet_image_model_t m = base;
+      m.model = r.model, m.H = r.H, m.W = r.W, m.psf_radius = r.R;
+      if (smcdet_mh_sweep_step_fused(&m, r.N, r.S, r.flags) != r.fused) {
+        std::printf("FAIL smcdet_mh_sweep_step_fused %s: want %d\n", r.name, r.fused);
+        ++bad;
+      }
+    }
+  }
+  // the errors the plan keeps (the product refuses the scalar-slots flag earlier)
+  MhPlanIn in{};
+  in.model = M, in.H = in.W = 128, in.R = 8, in.N = 4096, in.S = 10, in.T = 1, in.diag = true;
+  in.flags = SMCDET_MH_SCALAR_SLOTS;
+  const MhPlan p = mh_plan(in);
+  if (p.status != SMCDET_EUNSUPPORTED ||
+      std::strcmp(p.msg, "tiles above 4096 pixels: no fused step / scalar slots") != 0) {
+    std::printf("FAIL plan 128x128 scalar slots: status %d (%s)\n", p.status, p.msg);
+    ++bad;
+  }
+  return bad;
+}
+}  // namespace
 
 int main() {
   std::printf("%s abi %d\n", smcdet_version(), smcdet_abi_version());
@@ -294,6 +428,11 @@ int main() {
   EXPECT(smcdet_launch_timing_starts(ms, 2, &n), SMCDET_OK);
   if (n != 0) ++fails;
   EXPECT(smcdet_host_free(nullptr), SMCDET_OK);  // like free(NULL)
+  fails += plan_table(m);
+  // a diagnostic-only flag is refused before the buffers and the plan
+  EXPECT(smcdet_mh_sweep(&m, &p, &mh, nullptr, d, 1, 4, 10, nullptr, d, d, d, nullptr, d, d,
+                         nullptr, nullptr, 0, 0, nullptr, SMCDET_MH_SCALAR_SLOTS, nullptr, d, ws,
+                         nullptr, nullptr, nullptr), SMCDET_EUNSUPPORTED);
   std::printf("capi sanitizer driver: %d failure(s)\n", fails);
   return fails ? 1 : 0;
 }

@@ -3,7 +3,8 @@
 compiles (hipcc -Rpass-analysis=kernel-resource-usage on each source of the
 Makefile's SRCS): VGPRs, spilled VGPRs / SGPRs, scratch bytes per lane,
 occupancy.  MH sweep template order: <MODEL, REPLAY, FULL, PPL, PAIRED,
-TAIL, GL, PC, RV, TB>.  --diag: the diagnostic build (-DSMCDET_DIAG).
+TAIL, GL, PC, RV, TB, GEO> (the variants by name: smcdet_amd/csrc/mh_plan.h).
+--diag: the diagnostic build (-DSMCDET_DIAG).
     python scripts/kernel_resources.py > profiles/r06/kernel_resources.txt
     python scripts/kernel_resources.py --diag > profiles/r06/kernel_resources_diag.txt
 """
@@ -13,8 +14,9 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = ["common.hip", "model_kernels.hip", "mh_kernel.hip", "mala_kernel.hip",
-        "chain_kernel.hip", "smc_kernels.hip", "agg_kernel.hip"]
+with open(os.path.join(ROOT, "Makefile")) as mk:
+    SRCS = [os.path.basename(w)
+            for w in re.search(r"^SRCS := (.*)$", mk.read(), re.M).group(1).split()]
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 diag = "--diag" in sys.argv
 rows = []

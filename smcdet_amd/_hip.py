@@ -347,7 +347,8 @@ SOURCES = tuple(os.path.join(_REPO, p) for p in (
     "smcdet_amd/csrc/summary_kernel.hip", "smcdet_amd/csrc/convergence_kernel.hip",
     "smcdet_amd/csrc/extract_kernel.hip",
     "smcdet_amd/csrc/device.h", "smcdet_amd/csrc/render.h",
-    "smcdet_amd/csrc/mcmc.h", "smcdet_amd/csrc/tile.h", "include/smcdet_hip.h"))
+    "smcdet_amd/csrc/mcmc.h", "smcdet_amd/csrc/tile.h", "smcdet_amd/csrc/mh_plan.h",
+    "include/smcdet_hip.h"))
 
 
 def cached_struct(build):

@@ -41,6 +41,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "mh_plan.h"
 #include "render.h"
 #include "tile.h"
 
@@ -61,7 +62,6 @@ constexpr bool kDiag = true;
 constexpr bool kDiag = false;
 #endif
 
-constexpr int kMhWaves = 4;
 constexpr int kMhBlock = kMhWaves * kWave;
 constexpr int kSlots = 6;  // register-resident window passes (6*64 = 384 positions)
 // proposals computed together (3 lanes each): 21 entries = 63 lanes.  A batch
@@ -92,7 +92,7 @@ struct MhArgs {
   int generic_geometry;              // SMCDET_MH_GENERIC_GEOMETRY
   int no_write_through;              // SMCDET_MH_NO_WRITE_THROUGH (diagnostic)
   // rate_out stored write-through (wt_buffer, device.h): set by the host when
-  // the grid is one resident round of workgroups (launch_mh1) -- every wave's
+  // the grid is one resident round of workgroups (mh_plan.h) -- every wave's
   // image is then dirty in the L2 at the kernel's end, and the next launch
   // waits for the write-back; the epilogue alone reads it
   int write_through;
@@ -135,6 +135,10 @@ struct MhArgs {
 // callee-saved register convention pushed the sweep to 128 VGPRs and
 // scratch.
 constexpr int kTailMaxN = 8 * kTB;
+// mh_plan.h states these without the device headers
+static_assert(kMhPad == kWave && kMhMaxLdsPixels == kMaxLdsPixels && kMhTailMaxN == kTailMaxN &&
+                  kMhTabFloats * sizeof(float) == kTabNodes * sizeof(float4),
+              "mh_plan.h: constants out of step with device.h / tile.h");
 
 // truncated-normal cache at mean mu: Phi(lb) and log Z, Z = Phi(ub) - Phi(lb)
 // (distributions.py:33-35)
@@ -466,19 +470,13 @@ __device__ __forceinline__ void copy_out_regs(const float* lam, float* __restric
 // latency-bound.  Same-box A/B (C4, MH launch): 4 waves + all slot paths
 // 5.93 ms; 1-slot path at 4 waves 5.33; 6 waves (80 VGPRs, no spill) 5.17;
 // 7 waves 5.11; 8 waves (64 VGPRs, 15 spilled) 5.62.
-#ifndef SMCDET_SMALL_TILE_WAVES
-#define SMCDET_SMALL_TILE_WAVES 7
-#endif
 // (the replay instantiation of small tiles, tests only, holds the replayed
 // draws too: 6 waves per SIMD, 80 VGPRs, instead of spilling at 72; FULL
 // mode's register re-render of 65..1024-pixel tiles -- the reference's
 // arithmetic, a parity control, bit-identical to the loglik kernel's render --
 // runs at 2 waves per SIMD instead of spilling at 128 VGPRs)
 template <int PPL, bool REPLAY = false, bool FULL = false>
-constexpr int mh_waves_per_eu() {
-  return PPL == 1 ? (REPLAY ? SMCDET_SMALL_TILE_WAVES - 1 : SMCDET_SMALL_TILE_WAVES)
-                  : (FULL && PPL == 16 ? 2 : 4);
-}
+constexpr int mh_waves_per_eu() { return mh_wg_per_cu(PPL, REPLAY, FULL); }
 template <int PPL>
 constexpr int mh_slots() { return PPL == 1 ? 1 : kSlots; }
 
@@ -554,7 +552,7 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
   constexpr int kImg = (MODEL == SMCDET_MODEL_POISSON) ? 2 : 1;
   float* xs = smem;
   float* lg = smem + HWp;
-  float* lam = smem + kImg * HWp + wave * HWp;
+  float* lam = smem + mh_lds_rates(kImg, HWp) + wave * HWp;
   // kHT: the short head and tail of the register-render tiles above 64
   // pixels (the headline's 32x32 and every 65..1024-pixel shape), whose
   // launches are one resident round of waves all in the same phase.  The
@@ -602,8 +600,14 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
   [[maybe_unused]] const float4* tab = nullptr;
   [[maybe_unused]] const float tinv = a.tab_inv_h;
   if constexpr (TB) {
+    // mh_lds_tab(kImg, HWp, HW, a.S, RV, PC) written out: through the function
+    // the RV + TB instantiations compile to other code (8 more spilled SGPRs)
     const int off = ((kImg + kMhWaves) * HWp + (RV ? kMhWaves * HWp : 0) +
                      (PC ? kMhWaves * a.S * HW : 0) + 3) & ~3;
+    static_assert(mh_lds_tab(kImg, 1087, 1023, 10, RV, PC) ==
+                      (((kImg + kMhWaves) * 1087 + (RV ? kMhWaves * 1087 : 0) +
+                        (PC ? kMhWaves * 10 * 1023 : 0) + 3) & ~3),
+                  "the table's offset and mh_plan.h disagree");
     float4* t4 = reinterpret_cast<float4*>(smem + off);
     for (int i = threadIdx.x; i < kTabNodes; i += kMhBlock) t4[i] = a.psf_tab[i];
     tab = t4;
@@ -673,7 +677,7 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
 
   // the per-wave 1/v image (RV), after the rate images
   [[maybe_unused]] float* rv = nullptr;
-  if constexpr (RV) rv = lam + kMhWaves * HWp;
+  if constexpr (RV) rv = lam + mh_lds_region(HWp);
   double cur_ll = 0.0;  // tracked only in FULL mode (incremental mode works on deltas)
   if constexpr (GL && !FULL) {
     // the working image is rate_out's row: copy the ancestor's row in, or render
@@ -747,7 +751,7 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
   // merged access serves as it is, use rv.
   [[maybe_unused]] const float* rv_rd = nullptr;
   if constexpr (RV) {
-    rv_rd = GEO::kFixed ? lam + kMhWaves * (a.m.H * a.m.W + kWave) : rv;
+    rv_rd = GEO::kFixed ? lam + mh_lds_region(a.m.H * a.m.W + kWave) : rv;
     wave_sync();
     if (kHT && a.rate_in) {
       // rate_store_lds wrote the pixels' 1/v beside their rates: the dummy
@@ -776,7 +780,7 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
   // (2R+1)^2 window anchored at floor(loc) -- position_delta's old-window value
   [[maybe_unused]] float* pcw = nullptr;
   if constexpr (PC) {
-    pcw = smem + (kImg + kMhWaves) * HWp + wave * S * HW;
+    pcw = smem + mh_lds_cache(kImg, HWp) + wave * S * HW;
     const int ph = lane / m.W, pw = lane - ph * m.W;
     const float fph = (float)ph + 0.5f, fpw = (float)pw + 0.5f;
     for (int s = 0; s < S; ++s) {
@@ -1430,184 +1434,98 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
   }
 }
 
+// ---- from the plan (mh_plan.h) to the instantiation ---------------------------
+using MhKernel = void (*)(MhArgs);
+
+// The instantiation of the plan's variant at <MODEL, REPLAY, FULL, PPL>: each
+// is named here and nowhere else, behind the build's gate (null where this
+// build has none: the product compiles only what its plans reach).  The code
+// object lists the kernels in the order they are first named.
 template <int MODEL, bool REPLAY, bool FULL, int PPL>
-static int launch_mh1(const MhArgs& a_in, dim3 grid, size_t lds, hipStream_t st) {
-  // FULL mode never evaluates union-window slots: one instantiation
-  constexpr bool kPair = !FULL;
-  // (scalar slots: diagnostic build only, host-checked)
-  const bool paired = kPair && !(kDiag && a_in.scalar_slots);
-  // the fused tail exists only where tail_fusable() allows it
-  constexpr bool kTail = !FULL && PPL != 1;
-  const bool tail = kTail && paired && a_in.has_tail;
-  if (a_in.has_tail && !tail) return set_error(SMCDET_EINVAL, "fused step: unsupported shape");
-  // Write-through rate-image stores (the register-render tiles above 64
-  // pixels: kHT in the kernel) where every workgroup is resident at once
-  // (one workgroup per SIMD row: the instantiation's waves per SIMD are its
-  // workgroups per CU): all the images are then still dirty in the L2 when
-  // the kernel ends.  A launch of several rounds has written the earlier
-  // rounds' back by then, and keeps the plain stores it was measured with;
-  // the fused tail keeps its stores and fences as they are.
-  MhArgs a = a_in;
-  a.write_through =
-      PPL > 1 && !FULL && !tail && a.rate_out != nullptr && !a.no_write_through &&
-      (long long)grid.x * grid.y <=
-          (long long)device_cu_count() * mh_waves_per_eu<PPL, REPLAY, FULL>();
-  // The LDS-cached variants, richest first, where their workgroups per CU
-  // (the occupancy the instantiation is built for) still fit the 160 KiB:
-  // PC (small tiles) = the per-wave PSF cache, RV (M71, 65..1024 px) = the
-  // per-wave 1/v image, TB = the radial PSF table (diagnostic build: a.psf_tab
-  // set by the host for M71 models whose table passes its accuracy check).
-  auto fits = [&](size_t bytes, int wg_per_cu) {
-    return (size_t)wg_per_cu * (bytes + 1024) <= 160 * 1024;
-  };
-  [[maybe_unused]] auto with_tab = [&](size_t bytes) {
-    return ((bytes + 15) & ~(size_t)15) + (size_t)kTabNodes * sizeof(float4);
-  };
-  auto go_variant = [&](auto kern, size_t bytes) -> int {
-    int rc = ensure_lds((const void*)kern, bytes);
-    if (rc) return rc;
-    launch_sweep(kern, grid, dim3(kMhBlock), bytes, st, a);
-    return SMCDET_OK;
-  };
-  [[maybe_unused]] const bool tb = kDiag && a.psf_tab != nullptr && paired && !tail;
-  if constexpr (PPL == 1 && !FULL) {
-    // small tiles: the PSF cache (S rows of H*W floats per wave)
-    const size_t lds_pc = lds + (size_t)kMhWaves * a.S * a.m.H * a.m.W * sizeof(float);
-    constexpr int wg = SMCDET_SMALL_TILE_WAVES;
-    if constexpr (MODEL == SMCDET_MODEL_M71 && kDiag) {
-      if (tb && !a.no_psf_cache && fits(with_tab(lds_pc), wg))
-        return go_variant(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, true,
-                                          false, true>, with_tab(lds_pc));
-    }
-    if (paired && !a.no_psf_cache && fits(lds_pc, wg))
-      return go_variant(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, true>,
-                        lds_pc);
-    if constexpr (MODEL == SMCDET_MODEL_M71 && kDiag) {
-      if (tb && fits(with_tab(lds), wg))
-        return go_variant(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, false,
-                                          false, true>, with_tab(lds));
-    }
-  }
-  if constexpr (MODEL == SMCDET_MODEL_M71 && PPL > 1 && !FULL) {
-    // M71 register-render tiles: the 1/v image (HWp floats per wave) and / or
-    // the PSF table, at 4 workgroups per CU (4 waves per SIMD).  The 1/v image
-    // always fits at these sizes (9 (H*W + 64) floats per workgroup), so
-    // the product's only other M71 variant here is the fused tail's.
-    const size_t lds_rv = lds + (size_t)kMhWaves * (a.m.H * a.m.W + kWave) * sizeof(float);
-    const bool rv = paired && !tail && !(kDiag && a.no_rcp_cache);
-    if constexpr (kDiag) {
-      if (tb && rv && fits(with_tab(lds_rv), 4))
-        return go_variant(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, false,
-                                          true, true>, with_tab(lds_rv));
-      if (tb && fits(with_tab(lds), 4))
-        return go_variant(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, false,
-                                          false, true>, with_tab(lds));
-    }
-    if (rv && fits(lds_rv, 4)) {
-      // the headline geometry (32x32 tiles, R = 8) compiled in; same LDS bytes
-      if constexpr (PPL == 16) {
-        if (a.m.H == 32 && a.m.W == 32 && a.m.R == 8 && !a.generic_geometry)
-          return go_variant(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, false,
-                                            true, false, GeoFixed<32, 32, 8>>, lds_rv);
+static MhKernel mh_kernel_of(const MhPlan& p) {
+  constexpr bool kM71 = MODEL == SMCDET_MODEL_M71, kInc = !FULL;  // incremental: window slots
+  constexpr bool kReg = kM71 && kInc && PPL > 1;  // M71 register-render tiles: the 1/v image
+  switch (p.variant) {  // <.., PAIRED, TAIL, GL, PC, RV, TB, GEO>
+    case kMhPCTB:
+      if constexpr (kDiag && kM71 && kInc && PPL == 1)
+        return mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, true, false, true>;
+      break;
+    case kMhPC:
+      if constexpr (kInc && PPL == 1)
+        return mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, true>;
+      break;
+    case kMhRVTB:
+      if constexpr (kDiag && kReg)
+        return mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, false, true, true>;
+      break;
+    case kMhTB:
+      if constexpr (kDiag && kM71 && kInc && PPL > 0)
+        return mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, false, false, true>;
+      break;
+    case kMhRV:
+      if constexpr (kReg && PPL == 16) {
+        if (p.geo_fixed)
+          return mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, false, true, false,
+                                 GeoFixed<32, 32, 8>>;
       }
-      return go_variant(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, false, true>,
-                        lds_rv);
-    }
-    if constexpr (!kDiag) {
-      if (!tail) return set_error(SMCDET_EUNSUPPORTED, "M71 sweep: the 1/v image does not fit");
-    }
+      if constexpr (kReg)
+        return mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false, false, false, true>;
+      break;
+    case kMhTail:
+      if constexpr (kInc && PPL != 1) return mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, true>;
+      break;
+    case kMhPaired:  // (M71 register-render tiles take kMhRV or kMhTail in the product)
+      if constexpr (kInc && (kDiag || !kReg))
+        return mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, true, false>;
+      break;
+    case kMhUnpaired:
+      if constexpr (FULL || kDiag) return mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, false, false>;
+      break;
+    case kMhGL:  // mh_kernel_at
+      break;
   }
-  // M71 register-render tiles without the fused tail take the 1/v variant
-  // above: the plain paired instantiation is the diagnostic build's
-  // (SMCDET_MH_NO_RCP_CACHE) there; scalar slots likewise
-  constexpr bool kPlainPaired = kPair && (kDiag || !(MODEL == SMCDET_MODEL_M71 && PPL > 1));
-  constexpr bool kUnpaired = FULL || kDiag;
-  const void* fn = nullptr;
-  if (tail) {
-    if constexpr (kTail) fn = (const void*)mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, kPair, kTail>;
-  } else if (paired) {
-    if constexpr (kPlainPaired) fn = (const void*)mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, kPair, false>;
-  } else {
-    if constexpr (kUnpaired) fn = (const void*)mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, false, false>;
-  }
-  if (!fn) return set_error(SMCDET_EUNSUPPORTED, "MH sweep variant not in this build");
-  int rc = ensure_lds(fn, lds);
-  if (rc) return rc;
-  if (tail) {
-    if constexpr (kTail)
-      launch_sweep(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, kPair, kTail>, grid, dim3(kMhBlock),
-                   lds, st, a);
-  } else if (paired) {
-    if constexpr (kPlainPaired)
-      launch_sweep(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, kPair, false>, grid, dim3(kMhBlock),
-                   lds, st, a);
-  } else {
-    if constexpr (kUnpaired)
-      launch_sweep(mh_sweep_kernel<MODEL, REPLAY, FULL, PPL, false, false>, grid, dim3(kMhBlock),
-                   lds, st, a);
-  }
-  return SMCDET_OK;
-}
-
-// tiles above the LDS budget (M71 only; host-checked): paired slots, no
-// fused tail, no dynamic LDS
-template <int MODEL, bool REPLAY, bool FULL>
-static int launch_mh_gl(const MhArgs& a, dim3 grid, hipStream_t st) {
-  if (a.has_tail || (kDiag && a.scalar_slots))
-    return set_error(SMCDET_EUNSUPPORTED, "tiles above %d pixels: no fused step / scalar slots",
-                     kMaxLdsPixels);
-  constexpr bool kPair = !FULL;
-  launch_sweep(mh_sweep_kernel<MODEL, REPLAY, FULL, 0, kPair, false, true>, grid, dim3(kMhBlock),
-               0, st, a);
-  return SMCDET_OK;
+  return nullptr;
 }
 
 template <int MODEL, bool REPLAY, bool FULL>
-static int launch_mh_ppl(const MhArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  const int HW = a.m.H * a.m.W;
+static MhKernel mh_kernel_at(const MhPlan& p) {
   if constexpr (MODEL == SMCDET_MODEL_M71) {
-    if (HW > kMaxLdsPixels) return launch_mh_gl<MODEL, REPLAY, FULL>(a, grid, st);
+    if (p.variant == kMhGL) return mh_sweep_kernel<MODEL, REPLAY, FULL, 0, !FULL, false, true>;
   }
-  if (a.S <= kWave) {
-    if (HW <= 64) return launch_mh1<MODEL, REPLAY, FULL, 1>(a, grid, lds, st);
-    if (HW <= 256) return launch_mh1<MODEL, REPLAY, FULL, 4>(a, grid, lds, st);
-    if (HW <= 1024) return launch_mh1<MODEL, REPLAY, FULL, 16>(a, grid, lds, st);
-  }
-  return launch_mh1<MODEL, REPLAY, FULL, 0>(a, grid, lds, st);
+  return p.ppl == 1    ? mh_kernel_of<MODEL, REPLAY, FULL, 1>(p)
+         : p.ppl == 4  ? mh_kernel_of<MODEL, REPLAY, FULL, 4>(p)
+         : p.ppl == 16 ? mh_kernel_of<MODEL, REPLAY, FULL, 16>(p)
+                       : mh_kernel_of<MODEL, REPLAY, FULL, 0>(p);
 }
 
 template <int MODEL>
-static int launch_mh(const MhArgs& a, bool replay, bool full, dim3 grid, size_t lds,
-                     hipStream_t st) {
+static MhKernel mh_kernel_for(const MhPlan& p, bool replay, bool full) {
   if (replay)
-    return full ? launch_mh_ppl<MODEL, true, true>(a, grid, lds, st)
-                : launch_mh_ppl<MODEL, true, false>(a, grid, lds, st);
-  return full ? launch_mh_ppl<MODEL, false, true>(a, grid, lds, st)
-              : launch_mh_ppl<MODEL, false, false>(a, grid, lds, st);
+    return full ? mh_kernel_at<MODEL, true, true>(p) : mh_kernel_at<MODEL, true, false>(p);
+  return full ? mh_kernel_at<MODEL, false, true>(p) : mh_kernel_at<MODEL, false, false>(p);
 }
 
+static MhPlanIn mh_plan_in(const smcdet_image_model_t& m, int N, int S, int T, uint32_t flags,
+                           bool tail) {
+  return {m.model, m.H, m.W, m.psf_radius, N, S, T, flags, tail, tile_lds_bytes(N), kDiag};
+}
+
+static int launch_mh(const MhPlan& p, const MhArgs& a, bool replay, bool full, hipStream_t st) {
+  const MhKernel k = a.m.model == SMCDET_MODEL_M71
+                         ? mh_kernel_for<SMCDET_MODEL_M71>(p, replay, full)
+                         : mh_kernel_for<SMCDET_MODEL_POISSON>(p, replay, full);
+  if (!k) return set_error(SMCDET_EUNSUPPORTED, "MH sweep variant not in this build");
+  const int rc = ensure_lds((const void*)k, p.lds);
+  if (rc) return rc;
+  launch_sweep(k, dim3((a.N + kMhWaves - 1) / kMhWaves, a.T), dim3(kMhBlock), p.lds, st, a);
+  return SMCDET_OK;
+}
 }  // namespace smcdet
 
 using namespace smcdet;
 
 SMCDET_TRACE_READER(smcdet_trace_read_mh)
 SMCDET_WAVE_READER(smcdet_trace_read_waves)
-
-// the fused step's shape test; lds: the launch's dynamic LDS bytes
-static bool tail_fusable(const smcdet_image_model_t& m, int N, int S, uint32_t flags,
-                         size_t* lds) {
-  const size_t HWp = (size_t)m.H * m.W + kWave;
-  const size_t mh_lds =
-      ((m.model == SMCDET_MODEL_POISSON ? 2 : 1) * HWp + (size_t)kMhWaves * HWp) * sizeof(float);
-  const size_t need = mh_lds > tile_lds_bytes(N) ? mh_lds : tile_lds_bytes(N);
-  if (lds) *lds = need;
-  if (flags & (SMCDET_MH_FULL_RECOMPUTE | SMCDET_MH_SCALAR_SLOTS)) return false;
-  if (m.H * m.W > kMaxLdsPixels) return false;  // global-memory tiles: two launches
-  if (N % kMhWaves != 0 || N > kTailMaxN) return false;
-  if (S <= kWave && m.H * m.W <= 64) return false;  // small-tile instantiation (PPL = 1)
-  // 4 waves per SIMD = 4 workgroups per CU must still fit the 160 KiB LDS
-  return 4 * (need + 2048) <= 160 * 1024;
-}
 
 #ifdef SMCDET_DIAG  // the radial PSF table: diagnostic build only
 // ---- the radial PSF table (psf_tab, device.h) --------------------------------
@@ -1850,12 +1768,6 @@ static int mh_sweep_impl(const smcdet_image_model_t* model, const smcdet_prior_t
     a.r_accept = replay->trace_accept;
   }
   hipStream_t st = (hipStream_t)stream;
-  const size_t HWp = (size_t)model->H * model->W + kWave;
-  size_t lds = global_tile ? 0 :
-      ((model->model == SMCDET_MODEL_POISSON ? 2 : 1) * HWp + (size_t)kMhWaves * HWp) *
-      sizeof(float);
-  const dim3 grid((N + kMhWaves - 1) / kMhWaves, T);
-  bool split_tail = false;  // the tile pass as its own launch after the sweep
   TileArgs ta{};
   if (tail) {
     if (!loglik_out) return set_error(SMCDET_EINVAL, "the fused step needs loglik_out");
@@ -1903,16 +1815,6 @@ static int mh_sweep_impl(const smcdet_image_model_t* model, const smcdet_prior_t
       return set_error(SMCDET_EINVAL, "tail->live must be 8-byte aligned");
     ta.live = tail->live;
     ta.live_host = tail->live ? tail->live_host : nullptr;
-    size_t lds_f = 0;
-    if (!(tail->flags & SMCDET_SMC_TWO_LAUNCH) && tail_fusable(*model, N, S, flags, &lds_f)) {
-      a.tail = ta;
-      a.tail.go = nullptr;  // the sweep already returned when *go == 0
-      a.has_tail = 1;
-      lds = lds_f;
-    } else {
-      ta.go = go;
-      split_tail = true;
-    }
   }
   const bool full = (flags & SMCDET_MH_FULL_RECOMPUTE) != 0;
   a.ablate = flags & (SMCDET_MH_ABLATE_LIKELIHOOD | SMCDET_MH_ABLATE_PROPOSAL);
@@ -1938,12 +1840,25 @@ static int mh_sweep_impl(const smcdet_image_model_t* model, const smcdet_prior_t
     if (rc) return rc;
 #endif
   }
-  rc = a.m.model == SMCDET_MODEL_M71
-           ? launch_mh<SMCDET_MODEL_M71>(a, replay != nullptr, full, grid, lds, st)
-           : launch_mh<SMCDET_MODEL_POISSON>(a, replay != nullptr, full, grid, lds, st);
+  MhPlanIn in = mh_plan_in(*model, N, S, T, flags, tail != nullptr);
+  in.replay = replay != nullptr;
+  in.two_launch = tail && (tail->flags & SMCDET_SMC_TWO_LAUNCH);
+  in.rate_out = rate_out != nullptr;
+  in.psf_tab = a.psf_tab != nullptr;
+  in.cu_count = device_cu_count();
+  const MhPlan plan = mh_plan(in);
+  if (plan.status) return set_error(plan.status, "%s", plan.msg);
+  a.write_through = plan.write_through;
+  if (plan.tail == kMhTailFused) {
+    a.tail = ta;
+    a.tail.go = nullptr;  // the sweep already returned when *go == 0
+    a.has_tail = 1;
+  }
+  rc = launch_mh(plan, a, in.replay, full, st);
   if (rc) return rc;
   rc = check_launch("smcdet_mh_sweep");
-  if (rc || !split_tail) return rc;
+  if (rc || plan.tail != kMhTailSplit) return rc;
+  ta.go = go;
   // the tile pass on the sweep's log-likelihoods (tile.h tile_work: the same
   // work as smcdet_temper_reweight, replayed offsets and bins included)
   return launch_tile(ta, st);
@@ -1987,5 +1902,5 @@ extern "C" int smcdet_mh_sweep_step(const smcdet_image_model_t* model,
 extern "C" int smcdet_mh_sweep_step_fused(const smcdet_image_model_t* model, int32_t N, int32_t S,
                                           uint32_t flags) {
   if (!model) return 0;
-  return tail_fusable(*model, N, S, flags, nullptr) ? 1 : 0;
+  return mh_plan(mh_plan_in(*model, N, S, 1, flags, true)).tail == kMhTailFused ? 1 : 0;
 }
