@@ -1,10 +1,12 @@
 #!/usr/bin/env python
 """Interleaved A/B timing of MH-sweep variants at the C2 geometry (one
-process, rounds interleaved; reports median and min ms per launch).
+process, rounds interleaved; prints median and min ms per launch as one JSON
+line).
 
-Variants: incremental (default), the diagnostic ablations
-(SMCDET_MH_ABLATE_LIKELIHOOD / _PROPOSAL: timing only), full recompute, and
-the per-tile temper+reweight+resample launch."""
+Variants: incremental (default), full recompute, the per-tile
+temper+reweight+resample launch, and -- with the diagnostic build only,
+SMCDET_HIP_LIB=smcdet_amd/libsmcdet_hip_diag.so -- the timing-only ablations
+(flags 256 / 512), scalar slots (1024) and the --block-slots thresholds."""
 import argparse
 import json
 import os
@@ -38,13 +40,45 @@ def main():
     ap.add_argument("--tau", type=float, default=0.3)
     # library-independent inputs (torch CPU generator + the c2_moderate fixture
     # image), so that libraries whose prior/noise kernels draw different
-    # streams still time the MH sweep on identical states (scripts/ab_kernel.sh)
+    # streams still time the MH sweep on identical states (scripts/ab.py --cmd)
     ap.add_argument("--state", choices=["torch", "device"], default="torch")
     ap.add_argument("--warm", type=int, default=3, help="MH sweeps before timing (torch state)")
     # start every sweep from persisted rate images (as SMCsampler does) instead
     # of an initial render of all sources
     ap.add_argument("--persist", action="store_true")
     a = ap.parse_args()
+    # the variants, chosen before anything touches the device: name -> (full
+    # recompute, MH flags[, K]).  Flags 256 / 512 / 1024 and the "blk<n>"
+    # thresholds (SMCDET_MH_BLOCK_SLOTS, read at every launch; 0 = off) exist in
+    # the diagnostic build only: the product refuses the flags and ignores the
+    # threshold, so without that build they are left out of the default set
+    # and refused when asked for by name.
+    diag = _hip.is_diag()
+    variants = {"incremental": (False, 0),
+                "no_likelihood": (False, 256),
+                "no_proposal": (False, 512),
+                "no_both": (False, 768),
+                "scalar_slots": (False, 1024),
+                "no_block": (False, 16384)}
+    if a.full:
+        variants["full_recompute"] = (True, 0)
+    for kk in (0, 1, 25, 200):
+        variants[f"K={kk}"] = (False, 0, kk)
+    if a.only:
+        variants = {a.only: variants[a.only]}
+    envs = {}
+    for n in (a.block_slots.split(",") if a.block_slots else []):
+        variants[f"blk{n}"] = (False, 0)
+        envs[f"blk{n}"] = n
+    if a.variants:
+        variants = {k: variants[k] for k in a.variants.split(",")}
+    elif not a.only and not diag:
+        variants = {k: v for k, v in variants.items() if not v[1] & (256 | 512 | 1024)}
+    needs_diag = [k for k, v in variants.items() if k in envs or v[1] & (256 | 512 | 1024)]
+    if needs_diag and not diag:
+        sys.exit(f"mh_microbench: {', '.join(needs_diag)} need the diagnostic build, and "
+                 f"{_hip.LIB_PATH} ({_hip.version()}) is not one: run with "
+                 f"SMCDET_HIP_LIB={_hip.DIAG_LIB_PATH} (make diag)")
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     H, S, Np = a.tile, a.sources, a.particles
@@ -82,27 +116,6 @@ def main():
         mw.rng = PhiloxStream(123)
         for _ in range(a.warm):
             locs, fluxes, _ = mw.run(img, counts, locs, fluxes, tau, prior=prior, image_model=model)
-    variants = {"incremental": (False, 0),
-                "no_likelihood": (False, _hip.SMCDET_MH_ABLATE_LIKELIHOOD if hasattr(
-                    _hip, "SMCDET_MH_ABLATE_LIKELIHOOD") else 256),
-                "no_proposal": (False, 512),
-                "no_both": (False, 768),
-                "scalar_slots": (False, 1024),
-                "no_block": (False, 16384)}
-    if a.full:
-        variants["full_recompute"] = (True, 0)
-    for kk in (0, 1, 25, 200):
-        variants[f"K={kk}"] = (False, 0, kk)
-    if a.only:
-        variants = {a.only: variants[a.only]}
-    # block-form thresholds (SMCDET_MH_BLOCK_SLOTS, read at every launch):
-    # variant "blk<n>" = the default form with that threshold (0 = off)
-    envs = {}
-    for n in (a.block_slots.split(",") if a.block_slots else []):
-        variants[f"blk{n}"] = (False, 0)
-        envs[f"blk{n}"] = n
-    if a.variants:
-        variants = {k: variants[k] for k in a.variants.split(",")}
     times = {k: [] for k in variants}
     mhs = {}
     for k, v in variants.items():
@@ -181,7 +194,8 @@ def main():
     for k, v in out.items():
         if k in variants and not k.startswith("K="):
             v["particle_steps_per_s"] = steps / (v["median_ms"] * 1e-3)
-    print(json.dumps({"config": vars(a), "variants": out}, indent=1))
+    # one line, as bench.py prints its result (scripts/ab.py --cmd reads the last line)
+    print(json.dumps({"config": vars(a), "variants": out}))
 
 
 if __name__ == "__main__":

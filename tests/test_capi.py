@@ -202,9 +202,11 @@ def test_checked_wrapper_forwards_argtypes():
 
 
 def _mh_call(L, flags):
-    """smcdet_mh_sweep with valid descriptors and placeholder device pointers
-    (never dereferenced: the calls below stop at argument validation, or at
-    the launch on a machine without a GPU)."""
+    """smcdet_mh_sweep with valid descriptors, placeholder device pointers and
+    T = 0: every build stops in host validation (the product at the flag gate,
+    the diagnostic build at the `T=%d N=%d` check that follows it), so no path
+    reaches a launch and the pointers are never dereferenced, with or without
+    a GPU."""
     m = _hip.ImageModelC()
     m.model, m.H, m.W, m.psf_radius = 1, 32, 32, 8
     m.background, m.adu_per_nmgy, m.psf_norm = 100.0, 1.0, 1.0
@@ -221,7 +223,7 @@ def _mh_call(L, flags):
     mh.locs_max_h = mh.locs_max_w = 36.0
     P = [ctypes.c_void_p(0x100000 * (i + 1)) for i in range(16)]
     return L.smcdet_mh_sweep(ctypes.byref(m), ctypes.byref(p), ctypes.byref(mh), P[0], P[1],
-                             1, 64, 10, None, P[2], P[3], P[4], P[5], P[6], P[7], None, None,
+                             0, 64, 10, None, P[2], P[3], P[4], P[5], P[6], P[7], None, None,
                              1, 0, None, flags, P[8], P[9], P[10], None, None, None)
 
 
@@ -229,7 +231,8 @@ def test_product_refuses_diagnostic_flags_and_diag_build_takes_them():
     """The product library compiles only the dispatched MH variants and refuses
     the diagnostic ones (ablations 256/512, scalar slots 1024, PSF table 8192,
     no 1/v cache 4096: include/smcdet_hip.h) before any device work; the
-    diagnostic build (make diag) gets past that check."""
+    diagnostic build (make diag) gets past that check and stops at the next
+    one the call fails (T = 0)."""
     L = _hip.lib()
     assert not _hip.is_diag(L)
     for flag in (256, 512, 1024, 4096, 8192):
@@ -240,7 +243,10 @@ def test_product_refuses_diagnostic_flags_and_diag_build_takes_them():
         pytest.skip("diagnostic build not made")
     with _hip.diag_library() as D:
         assert _hip.lib() is D and _hip.is_diag(D)
-        for flag in (256, 1024, 4096):
-            _mh_call(D, flag)
-            assert b"diagnostic build" not in D.smcdet_last_error(), flag
+        for flag in (256, 512, 1024, 4096, 8192):
+            rc = _mh_call(D, flag)
+            err = D.smcdet_last_error()
+            assert rc == -2, (flag, rc, err)
+            assert b"T=0" in err, (flag, err)
+            assert b"diagnostic build" not in err, flag
     assert _hip.lib() is L
