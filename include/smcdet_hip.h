@@ -43,6 +43,20 @@ extern "C" {
 /* priors */
 #define SMCDET_PRIOR_M71 1    /* M71Prior: Poisson count, uniform locs, truncated-Pareto flux */
 #define SMCDET_PRIOR_PARETO 2 /* ParetoStarPrior: uniform count, uniform locs, Pareto flux   */
+/* StarPrior (smcdet/prior.py:125-154): uniform count, uniform locs, Normal
+ * flux.  Added under SMCDET_ABI_VERSION 20 (additive: a new value of `kind`;
+ * smcdet_prior_t keeps its layout, see the field reuse there).  Taken by
+ * smcdet_log_prior, smcdet_prior_sample, and by smcdet_mh_sweep /
+ * smcdet_mh_sweep_step / smcdet_mala_sweep with SMCDET_MODEL_POISSON (every
+ * use in the reference); with SMCDET_MODEL_M71, and in smcdet_mh_chain and
+ * smcdet_aggregate_sweep, it returns SMCDET_EUNSUPPORTED before any device
+ * work.  A Normal flux may be <= 0: no zero-flux substitution (prior.py:151-154
+ * has none) and no log(flux) in the prior term of the sweeps.
+ * smcdet_prior_sample draws flux = mean + stdev * sqrt(2) * erfinv(2u' - 1)
+ * with u' = min(max(u, 2^-25), 1 - 2^-24): u = 0 (which the generator can
+ * return) maps to mean - 5.42 stdev, u = 1 - 2^-24 to mean + 5.29 stdev, both
+ * finite. */
+#define SMCDET_PRIOR_NORMAL 3
 
 /* resampling */
 #define SMCDET_RESAMPLE_MULTINOMIAL 0
@@ -131,7 +145,7 @@ typedef struct smcdet_image_model {
   float noise_multiplicative;
 } smcdet_image_model_t;
 
-/* Prior (smcdet/prior.py:8-75, :78-101, :157-189, :192-226). */
+/* Prior (smcdet/prior.py:8-75, :78-101, :125-154, :157-189, :192-226). */
 typedef struct smcdet_prior {
   int32_t kind;           /* SMCDET_PRIOR_* */
   int32_t min_objects, max_objects;
@@ -139,9 +153,10 @@ typedef struct smcdet_prior {
   float loc_high_h;       /* H + pad */
   float loc_high_w;       /* W + pad */
   float poisson_mean;     /* M71: counts_rate*(H+2pad)*(W+2pad) */
-  float flux_alpha;
-  float flux_lower;       /* M71: truncated-Pareto lower; PARETO: flux_scale */
-  float flux_upper;       /* M71: truncated-Pareto upper; PARETO: unused */
+  float flux_alpha;       /* NORMAL: unused */
+  float flux_lower;       /* M71: truncated-Pareto lower; PARETO: flux_scale; NORMAL: flux_mean */
+  float flux_upper;       /* M71: truncated-Pareto upper; PARETO: unused; NORMAL: flux_stdev
+                           * (finite, > 0; flux_mean finite: else SMCDET_EINVAL) */
 } smcdet_prior_t;
 
 /* Single-component MH kernel (smcdet/kernel.py:7-24). */

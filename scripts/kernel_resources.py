@@ -3,7 +3,9 @@
 compiles (hipcc -Rpass-analysis=kernel-resource-usage on each source of the
 Makefile's SRCS): VGPRs, spilled VGPRs / SGPRs, scratch bytes per lane,
 occupancy.  MH sweep template order: <MODEL, REPLAY, FULL, PPL, PAIRED,
-TAIL, GL, PC, RV, TB, GEO> (the variants by name: smcdet_amd/csrc/mh_plan.h).
+TAIL, GL, PC, RV, TB, GEO, FP> (the variants by name: smcdet_amd/csrc/mh_plan.h;
+FP: the flux-prior family, 0 power law, 1 Normal), MALA: <MODEL, REPLAY, FP>.
+Sources named as arguments limit the table to them.
 --diag: the diagnostic build (-DSMCDET_DIAG).
     python scripts/kernel_resources.py > profiles/r06/kernel_resources.txt
     python scripts/kernel_resources.py --diag > profiles/r06/kernel_resources_diag.txt

@@ -20,6 +20,7 @@ SMCDET_MODEL_M71 = 1
 SMCDET_MODEL_POISSON = 2
 SMCDET_PRIOR_M71 = 1
 SMCDET_PRIOR_PARETO = 2
+SMCDET_PRIOR_NORMAL = 3  # StarPrior: uniform count, uniform locs, Normal flux
 SMCDET_RESAMPLE_MULTINOMIAL = 0
 SMCDET_RESAMPLE_SYSTEMATIC = 1
 SMCDET_MH_FULL_RECOMPUTE = 1

@@ -276,6 +276,8 @@ class Aggregate(object):
         if isinstance(MutationKernel, SingleComponentMALA):
             raise NotImplementedError("Aggregate runs SingleComponentMH moves (the fused "
                                       "aggregation sweep has no MALA variant)")
+        from .prior import refuse_star_prior
+        refuse_star_prior(Prior, where="Aggregate")
         self.Prior = deepcopy(Prior)
         self.ImageModel = deepcopy(ImageModel)
         self.MutationKernel = deepcopy(MutationKernel)

@@ -372,6 +372,10 @@ extern "C" int smcdet_aggregate_sweep(
   if (need < 0) return (int)need;
   int rc = validate_prior(prior);
   if (rc) return rc;
+  if (prior->kind == SMCDET_PRIOR_NORMAL)
+    return set_error(SMCDET_EUNSUPPORTED,
+                     "smcdet_aggregate_sweep: the Normal flux prior (SMCDET_PRIOR_NORMAL, "
+                     "StarPrior) is not supported");
   if (!mh) return set_error(SMCDET_EINVAL, "mh params are null");
   if (!tiled_image || !temperature || !counts_in || !locs_in || !fluxes_in || !locs_out ||
       !fluxes_out)

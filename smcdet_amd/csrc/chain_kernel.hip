@@ -309,6 +309,12 @@ extern "C" int smcdet_mh_chain(const smcdet_image_model_t* model, const smcdet_p
   if (rc) return rc;
   rc = validate_prior(prior);
   if (rc) return rc;
+  // (the reference's MHsampler takes its flux bounds from the prior's
+  // flux_lower / flux_upper, which StarPrior does not have)
+  if (prior->kind == SMCDET_PRIOR_NORMAL)
+    return set_error(SMCDET_EUNSUPPORTED,
+                     "smcdet_mh_chain: the Normal flux prior (SMCDET_PRIOR_NORMAL, StarPrior) "
+                     "is not supported");
   if (!mh || !tiled_image || !counts || !locs_state || !fluxes_state || !locs_out ||
       !fluxes_out)
     return set_error(SMCDET_EINVAL, "null buffer");

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include <atomic>
+#include <cmath>
 
 #include "device.h"
 
@@ -144,6 +145,16 @@ DevPrior make_dev_prior(const smcdet_prior_t& p) {
     d.count_c1 = p.poisson_mean;
     // TruncatedPareto.logpdf_norm_const (distributions.py:69-74)
     d.flux_c = (float)(log(a) + a * log(L) + a * log(U) - log(pow(U, a) - pow(L, a)));
+  } else if (p.kind == SMCDET_PRIOR_NORMAL) {
+    d.count_c0 = (float)log(1.0 / (double)(p.max_objects - p.min_objects + 1));
+    // Normal(mean, sd).log_prob: -log(sd) - log(2 pi)/2 - (f - mean)^2 / (2 sd^2);
+    // the constants in the power-law fields (device.h nrm_*)
+    const double sd = p.flux_upper;
+    d.flux_c = (float)(-log(sd) - 0.5 * log(2.0 * M_PI));
+    d.ap1 = (float)(1.0 / (2.0 * sd * sd));
+    d.alpha = (float)(1.0 / (sd * sd));
+    d.lower = p.flux_lower;
+    d.upper = p.flux_upper;
   } else {
     d.count_c0 = (float)log(1.0 / (double)(p.max_objects - p.min_objects + 1));
     // Pareto(scale, alpha).log_prob: log(alpha) + alpha*log(scale) - (alpha+1)*log(f)
@@ -154,8 +165,17 @@ DevPrior make_dev_prior(const smcdet_prior_t& p) {
 
 int validate_prior(const smcdet_prior_t* p) {
   if (!p) return set_error(SMCDET_EINVAL, "prior is null");
-  if (p->kind != SMCDET_PRIOR_M71 && p->kind != SMCDET_PRIOR_PARETO)
+  if (p->kind != SMCDET_PRIOR_M71 && p->kind != SMCDET_PRIOR_PARETO &&
+      p->kind != SMCDET_PRIOR_NORMAL)
     return set_error(SMCDET_EINVAL, "unknown prior kind %d", p->kind);
+  if (p->kind == SMCDET_PRIOR_NORMAL) {  // (flux_lower, flux_upper) = (mean, stdev)
+    if (!std::isfinite(p->flux_lower))
+      return set_error(SMCDET_EINVAL, "Normal flux prior: mean %g is not finite",
+                       (double)p->flux_lower);
+    if (!std::isfinite(p->flux_upper) || !(p->flux_upper > 0.f))
+      return set_error(SMCDET_EINVAL, "Normal flux prior: stdev %g must be finite and > 0",
+                       (double)p->flux_upper);
+  }
   if (p->min_objects < 0 || p->max_objects < p->min_objects || p->max_objects > 4096)
     return set_error(SMCDET_EUNSUPPORTED, "objects %d..%d outside 0..4096", p->min_objects,
                      p->max_objects);

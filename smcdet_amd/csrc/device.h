@@ -618,13 +618,41 @@ struct DevPrior {
   int kind;
   float lo, hi_h, hi_w;      // location box: [lo, hi_h) x [lo_w, hi_w)
   float lo_w;
-  float count_c0, count_c1;  // M71: log(mu), mu ; PARETO: log(1/k), unused
+  float count_c0, count_c1;  // M71: log(mu), mu ; PARETO, NORMAL: log(1/k), unused
   int min_objects, max_objects;
   float flux_c;              // log-normaliser of the flux density
   float ap1;                 // alpha + 1
   float alpha, lower, upper;
+  // SMCDET_PRIOR_NORMAL reuses the power-law fields (the struct is a by-value
+  // argument of every sweep: its size is part of their kernarg layout) through
+  // the accessors below: flux_c = -log(sd) - log(2 pi)/2, ap1 = 1/(2 sd^2),
+  // alpha = 1/sd^2, lower = mean, upper = sd
   float loc_lp_h, loc_lp_w;  // -log(high - low) per coordinate
 };
+
+// the Normal flux family's constants in the fields it reuses
+__host__ __device__ __forceinline__ float nrm_inv_2var(const DevPrior& p) { return p.ap1; }
+__host__ __device__ __forceinline__ float nrm_inv_var(const DevPrior& p) { return p.alpha; }
+__host__ __device__ __forceinline__ float nrm_mean(const DevPrior& p) { return p.lower; }
+__host__ __device__ __forceinline__ float nrm_sd(const DevPrior& p) { return p.upper; }
+
+// The flux-prior family a sweep is compiled for (a template argument: the
+// power-law instantiations keep their code).  kFluxPow: M71Prior and
+// ParetoStarPrior, log p(f) = c - (alpha + 1) log f.  kFluxNormal: StarPrior,
+// log p(f) = c - (f - mean)^2 / (2 sd^2); nothing in it takes log f (a Normal
+// flux may be <= 0) and a flux of 0 is not replaced.
+constexpr int kFluxPow = 0, kFluxNormal = 1;
+// log p(fn) - log p(f) of an active source
+template <int FP>
+__device__ __forceinline__ float flux_prior_delta(const DevPrior& pr, float f, float fn,
+                                                  float lf, float lfn) {
+  if constexpr (FP == kFluxNormal) {
+    const float d0 = f - nrm_mean(pr), d1 = fn - nrm_mean(pr);
+    return -nrm_inv_2var(pr) * (d1 * d1 - d0 * d0);
+  } else {
+    return -pr.ap1 * (lfn - lf);
+  }
+}
 
 DevPrior make_dev_prior(const smcdet_prior_t& p);  // common.hip
 int validate_prior(const smcdet_prior_t* p);        // common.hip

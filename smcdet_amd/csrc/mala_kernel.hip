@@ -12,7 +12,8 @@
 //     d log_target / d rate per pixel (M71: (x-l)/v + eta (x-l)^2/(2v^2) -
 //     eta/(2v); Poisson: x/l - 1) times d rate / d(h, w, f) = g psf, g f
 //     dpsf/dh, g f dpsf/dw, summed over the source's clipped PSF window (one
-//     pass, <= (2R+1)^2 positions), plus the flux prior's -(alpha+1)/f;
+//     pass, <= (2R+1)^2 positions), plus the flux prior's -(alpha+1)/f (power
+//     law) or -(f - mean)/sd^2 (FP = kFluxNormal, StarPrior: Poisson model);
 //   * proposal (kernel.py:168-190): truncated normals around x + step^2/2 *
 //     grad, lanes 0/1/2 one dimension each, in the reference's float32
 //     operation order (distributions.py:22-52): Normal.cdf saturates to 0/1
@@ -73,8 +74,10 @@ struct MalaArgs {
 
 constexpr int kKeep = 5;  // register-resident new-window slots (5*64 >= 17*17)
 
-template <int MODEL, bool REPLAY>
+template <int MODEL, bool REPLAY, int FP = kFluxPow>
 __global__ __launch_bounds__(kMalaBlock, 4) void mala_sweep_kernel(MalaArgs a) {
+  static_assert(FP == kFluxPow || MODEL == SMCDET_MODEL_POISSON,
+                "Normal flux prior: the Poisson model's sweep");
   extern __shared__ float smem[];
   __shared__ int wg_acc, wg_done;
   if (a.go && *a.go == 0) return;
@@ -193,7 +196,11 @@ __global__ __launch_bounds__(kMalaBlock, 4) void mala_sweep_kernel(MalaArgs a) {
     const float ud = d == 0 ? readlane(ru1, kl) : (d == 1 ? readlane(ru2, kl) : readlane(ru3, kl));
     const float h = readlane(sh, j), w = readlane(sw, j), f = readlane(sfx, j);
     const bool active = (float)j < count;
-    const float ft = f == 0.f ? a.pr.lower : f;  // prior.py:189, :226
+    // (FP == kFluxNormal: StarPrior, prior.py:151-154, substitutes nothing, and
+    // its flux gradient is -(f - mean) / sd^2)
+    float ft, gf;
+    if constexpr (FP == kFluxPow) ft = f == 0.f ? a.pr.lower : f;  // prior.py:189, :226
+    else ft = f;
 
     // ---- gradient at the current state (kernel.py:157-166) ------------------
     const Window qo = window_of(m, h, w);
@@ -201,7 +208,10 @@ __global__ __launch_bounds__(kMalaBlock, 4) void mala_sweep_kernel(MalaArgs a) {
     grad_at(h, w, qo, g0);
     const float gh = tau * ((gs * f) * (-2.0f * g0[0]));
     const float gw = tau * ((gs * f) * (-2.0f * g0[1]));
-    const float gf = tau * (gs * g0[2]) - (active ? a.pr.ap1 / ft : 0.f);
+    if constexpr (FP == kFluxPow)
+      gf = tau * (gs * g0[2]) - (active ? a.pr.ap1 / ft : 0.f);
+    else
+      gf = tau * (gs * g0[2]) - (active ? (f - nrm_mean(a.pr)) * nrm_inv_var(a.pr) : 0.f);
 
     // ---- proposal (kernel.py:168-190), lane d: dimension d -------------------
     const float cur = d == 0 ? h : (d == 1 ? w : f);
@@ -274,10 +284,16 @@ __global__ __launch_bounds__(kMalaBlock, 4) void mala_sweep_kernel(MalaArgs a) {
       scr[a.W2 + i] = lo + dl;
     }
     const float dll = wave_sum(dsum);
-    const float fnt = fn == 0.f ? a.pr.lower : fn;
+    float fnt, pgf_;
+    if constexpr (FP == kFluxPow) fnt = fn == 0.f ? a.pr.lower : fn;
+    else fnt = fn;
     const float pgh_ = tau * ((gs * fn) * (-2.0f * wave_sum(pgh)));
     const float pgw_ = tau * ((gs * fn) * (-2.0f * wave_sum(pgw)));
-    const float pgf_ = tau * (gs * wave_sum(pgf)) - (active ? a.pr.ap1 / fnt : 0.f);
+    if constexpr (FP == kFluxPow)
+      pgf_ = tau * (gs * wave_sum(pgf)) - (active ? a.pr.ap1 / fnt : 0.f);
+    else
+      pgf_ = tau * (gs * wave_sum(pgf)) -
+             (active ? (fn - nrm_mean(a.pr)) * nrm_inv_var(a.pr) : 0.f);
 
     // ---- reverse proposal density q(z | z') (kernel.py:199-224) -------------
     const float pgd = d == 0 ? pgh_ : (d == 1 ? pgw_ : pgf_);
@@ -295,7 +311,11 @@ __global__ __launch_bounds__(kMalaBlock, 4) void mala_sweep_kernel(MalaArgs a) {
     // at or beyond the uniform prior's `high` has log prior -inf (nan for a
     // masked source): both reject
     const bool outside = hn >= a.pr.hi_h || wn >= a.pr.hi_w || hn < a.pr.lo || wn < a.pr.lo;
-    const float dprior = active ? -a.pr.ap1 * (fast_log(fnt) - fast_log(ft)) : 0.f;
+    float dprior;  // (the Normal family takes no logarithm of a flux)
+    if constexpr (FP == kFluxPow)
+      dprior = active ? -a.pr.ap1 * (fast_log(fnt) - fast_log(ft)) : 0.f;
+    else
+      dprior = active ? flux_prior_delta<FP>(a.pr, ft, fnt, 0.f, 0.f) : 0.f;
     const float dlt = dprior + tau * dll;
     const float big = 1e30f;
     float la;
@@ -367,16 +387,16 @@ __global__ __launch_bounds__(kMalaBlock, 4) void mala_sweep_kernel(MalaArgs a) {
   }
 }
 
-template <int MODEL>
+template <int MODEL, int FP = kFluxPow>
 static int launch_mala(const MalaArgs& a, bool replay, dim3 grid, size_t lds, hipStream_t st) {
-  const void* fn = replay ? (const void*)mala_sweep_kernel<MODEL, true>
-                          : (const void*)mala_sweep_kernel<MODEL, false>;
+  const void* fn = replay ? (const void*)mala_sweep_kernel<MODEL, true, FP>
+                          : (const void*)mala_sweep_kernel<MODEL, false, FP>;
   int rc = ensure_lds(fn, lds);
   if (rc) return rc;
   if (replay)
-    launch_sweep(mala_sweep_kernel<MODEL, true>, grid, dim3(kMalaBlock), lds, st, a);
+    launch_sweep(mala_sweep_kernel<MODEL, true, FP>, grid, dim3(kMalaBlock), lds, st, a);
   else
-    launch_sweep(mala_sweep_kernel<MODEL, false>, grid, dim3(kMalaBlock), lds, st, a);
+    launch_sweep(mala_sweep_kernel<MODEL, false, FP>, grid, dim3(kMalaBlock), lds, st, a);
   return SMCDET_OK;
 }
 
@@ -399,6 +419,10 @@ extern "C" int smcdet_mala_sweep(const smcdet_image_model_t* model, const smcdet
   rc = validate_prior(prior);
   if (rc) return rc;
   if (!mala) return set_error(SMCDET_EINVAL, "mala params are null");
+  if (prior->kind == SMCDET_PRIOR_NORMAL && model->model != SMCDET_MODEL_POISSON)
+    return set_error(SMCDET_EUNSUPPORTED,
+                     "smcdet_mala_sweep: the Normal flux prior (SMCDET_PRIOR_NORMAL, StarPrior) "
+                     "runs with SMCDET_MODEL_POISSON only");
   if (!tiled_image || !temperature || !counts_in || !locs_in || !fluxes_in || !locs_out ||
       !fluxes_out || !acc_rate || !acc_count)
     return set_error(SMCDET_EINVAL, "null buffer");
@@ -469,7 +493,9 @@ extern "C" int smcdet_mala_sweep(const smcdet_image_model_t* model, const smcdet
                      sizeof(float);
   const dim3 grid((N + kMalaWaves - 1) / kMalaWaves, T);
   hipStream_t st = (hipStream_t)stream;
-  rc = a.m.model == SMCDET_MODEL_M71 ? launch_mala<SMCDET_MODEL_M71>(a, replay != nullptr, grid, lds, st)
+  rc = a.pr.kind == SMCDET_PRIOR_NORMAL
+           ? launch_mala<SMCDET_MODEL_POISSON, kFluxNormal>(a, replay != nullptr, grid, lds, st)
+       : a.m.model == SMCDET_MODEL_M71 ? launch_mala<SMCDET_MODEL_M71>(a, replay != nullptr, grid, lds, st)
                                      : launch_mala<SMCDET_MODEL_POISSON>(a, replay != nullptr, grid, lds, st);
   if (rc) return rc;
   return check_launch("smcdet_mala_sweep");

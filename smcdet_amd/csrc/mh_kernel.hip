@@ -515,13 +515,17 @@ struct GeoFixed {
 // floating-point operation and its order are GeoRun's, so results are
 // bit-identical.
 template <int MODEL, bool REPLAY, bool FULL, int PPL, bool PAIRED, bool TAIL, bool GL = false,
-          bool PC = false, bool RV = false, bool TB = false, class GEO = GeoRun>
+          bool PC = false, bool RV = false, bool TB = false, class GEO = GeoRun,
+          int FP = kFluxPow>
 __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) void mh_sweep_kernel(
     MhArgs a) {
   static_assert(!GEO::kFixed || (RV && PPL > 1 && GEO::kH * GEO::kW <= 64 * PPL &&
                                  GEO::kH * GEO::kW > 16 * PPL),
                 "compiled-in geometry: the 1/v variant at its own PPL");
   static_assert(!PC || (PPL == 1 && !FULL && !GL && !TAIL), "PSF cache: small incremental tiles");
+  static_assert(FP == kFluxPow || (MODEL == SMCDET_MODEL_POISSON && !GL && !RV && !TB &&
+                                   !GEO::kFixed),
+                "Normal flux prior: the Poisson model's sweeps");
   static_assert(!RV || (MODEL == SMCDET_MODEL_M71 && PPL > 1 && !FULL && !GL && !TAIL && PAIRED),
                 "1/v cache: M71 register-render tiles, incremental, paired");
   static_assert(!TB || (MODEL == SMCDET_MODEL_M71 && PPL > 0 && !FULL && !GL && !TAIL && PAIRED),
@@ -894,7 +898,9 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
     const float lf_cur = fast_log(mu);  // (lane 3b+2: mu = the current flux)
     bampo = m.g * mu * psf_scale<MODEL>(m);
     bampn = m.g * bx * psf_scale<MODEL>(m);
-    bdp = ((float)j < count) ? -a.pr.ap1 * (blf - lf_cur) : 0.0f;
+    // (FP: power law -(alpha+1) (log f' - log f), or the Normal family's
+    // -((f'-mean)^2 - (f-mean)^2) / (2 sd^2), which reads no log f)
+    bdp = ((float)j < count) ? flux_prior_delta<FP>(a.pr, mu, bx, lf_cur, blf) : 0.0f;
     // a location proposal clamped onto the box's upper edge (distributions.py:48)
     // has log prior -inf (Uniform.log_prob(high), prior.py:73): its lane's
     // term carries it into the summed Hastings + prior term of lane 3b+2
@@ -1437,8 +1443,55 @@ __global__ __launch_bounds__(kMhBlock, (mh_waves_per_eu<PPL, REPLAY, FULL>())) v
 // ---- from the plan (mh_plan.h) to the instantiation ---------------------------
 using MhKernel = void (*)(MhArgs);
 
+// The Normal flux family (StarPrior) at <REPLAY, FULL, PPL>: the Poisson
+// model's plans only -- PC, fused tail, paired, and unpaired under full
+// recompute.
+template <bool REPLAY, bool FULL, int PPL>
+static MhKernel mh_kernel_normal_of(const MhPlan& p) {
+  constexpr int M = SMCDET_MODEL_POISSON;
+  constexpr bool kInc = !FULL;
+  switch (p.variant) {  // <.., PAIRED, TAIL, GL, PC, RV, TB, GEO, FP>
+    case kMhPC:
+      if constexpr (kInc && PPL == 1)
+        return mh_sweep_kernel<M, REPLAY, FULL, PPL, true, false, false, true, false, false,
+                               GeoRun, kFluxNormal>;
+      break;
+    case kMhTail:
+      if constexpr (kInc && PPL != 1)
+        return mh_sweep_kernel<M, REPLAY, FULL, PPL, true, true, false, false, false, false,
+                               GeoRun, kFluxNormal>;
+      break;
+    case kMhPaired:
+      if constexpr (kInc)
+        return mh_sweep_kernel<M, REPLAY, FULL, PPL, true, false, false, false, false, false,
+                               GeoRun, kFluxNormal>;
+      break;
+    case kMhUnpaired:
+      if constexpr (FULL)
+        return mh_sweep_kernel<M, REPLAY, FULL, PPL, false, false, false, false, false, false,
+                               GeoRun, kFluxNormal>;
+      break;
+    default:
+      break;
+  }
+  return nullptr;
+}
+
+template <bool REPLAY, bool FULL>
+static MhKernel mh_kernel_normal_at(const MhPlan& p) {
+  return p.ppl == 1    ? mh_kernel_normal_of<REPLAY, FULL, 1>(p)
+         : p.ppl == 4  ? mh_kernel_normal_of<REPLAY, FULL, 4>(p)
+         : p.ppl == 16 ? mh_kernel_normal_of<REPLAY, FULL, 16>(p)
+                       : mh_kernel_normal_of<REPLAY, FULL, 0>(p);
+}
+
+static MhKernel mh_kernel_normal_for(const MhPlan& p, bool replay, bool full) {
+  if (replay) return full ? mh_kernel_normal_at<true, true>(p) : mh_kernel_normal_at<true, false>(p);
+  return full ? mh_kernel_normal_at<false, true>(p) : mh_kernel_normal_at<false, false>(p);
+}
+
 // The instantiation of the plan's variant at <MODEL, REPLAY, FULL, PPL>: each
-// is named here and nowhere else, behind the build's gate (null where this
+// is named here (the Normal flux family's: above) and nowhere else, behind the build's gate (null where this
 // build has none: the product compiles only what its plans reach).  The code
 // object lists the kernels in the order they are first named.
 template <int MODEL, bool REPLAY, bool FULL, int PPL>
@@ -1511,7 +1564,10 @@ static MhPlanIn mh_plan_in(const smcdet_image_model_t& m, int N, int S, int T, u
 }
 
 static int launch_mh(const MhPlan& p, const MhArgs& a, bool replay, bool full, hipStream_t st) {
-  const MhKernel k = a.m.model == SMCDET_MODEL_M71
+  // (the Normal family reaches here with the Poisson model only: mh_sweep_impl)
+  const MhKernel k = a.pr.kind == SMCDET_PRIOR_NORMAL
+                         ? mh_kernel_normal_for(p, replay, full)
+                     : a.m.model == SMCDET_MODEL_M71
                          ? mh_kernel_for<SMCDET_MODEL_M71>(p, replay, full)
                          : mh_kernel_for<SMCDET_MODEL_POISSON>(p, replay, full);
   if (!k) return set_error(SMCDET_EUNSUPPORTED, "MH sweep variant not in this build");
@@ -1680,6 +1736,10 @@ static int mh_sweep_impl(const smcdet_image_model_t* model, const smcdet_prior_t
   rc = validate_prior(prior);
   if (rc) return rc;
   if (!mh) return set_error(SMCDET_EINVAL, "mh params are null");
+  if (prior->kind == SMCDET_PRIOR_NORMAL && model->model != SMCDET_MODEL_POISSON)
+    return set_error(SMCDET_EUNSUPPORTED,
+                     "smcdet_mh_sweep: the Normal flux prior (SMCDET_PRIOR_NORMAL, StarPrior) "
+                     "runs with SMCDET_MODEL_POISSON only");
   // (before the buffers are looked at: which flags a build takes -- the other
   // diagnostic ones, SMCDET_MH_NO_PSF_CACHE / _NO_BLOCK / _GENERIC_GEOMETRY, run
   // in the product too -- shows without a device)

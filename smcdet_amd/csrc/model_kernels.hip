@@ -167,7 +167,8 @@ __global__ void sample_image_kernel(DevModel m, const float* __restrict__ rate, 
 // priors
 // ---------------------------------------------------------------------------
 // M71Prior.log_prob (prior.py:220-226, :67-75) / ParetoStarPrior.log_prob
-// (prior.py:183-189): thread per particle
+// (prior.py:183-189) / StarPrior.log_prob (prior.py:151-154: Normal fluxes, no
+// zero-flux substitution): thread per particle
 // tile_boxes [T,4] (lo_h, lo_w, hi_h, hi_w), nullable: per-tile location boxes
 // (a partition of the padded image, SMCDET_ABI 12); the Poisson count mean
 // scales with the box area
@@ -194,6 +195,11 @@ __global__ void log_prior_kernel(DevPrior pr, const float* __restrict__ counts,
     const float lw = (w >= pr.lo_w && w < pr.hi_w) ? pr.loc_lp_w : -INFINITY;
     sl += lh + lw;
     float f = fluxes[i * S + s];
+    if (pr.kind == SMCDET_PRIOR_NORMAL) {
+      const float df = f - nrm_mean(pr);
+      sfl += pr.flux_c - nrm_inv_2var(pr) * (df * df);
+      continue;
+    }
     if (f == 0.f) f = pr.lower;
     sfl += pr.flux_c - pr.ap1 * logf(f);
   }
@@ -239,6 +245,13 @@ __global__ void prior_sample_kernel(DevPrior pr, int T, int N, int n_per_count, 
     const float Ua = powf(pr.upper, pr.alpha), La = powf(pr.lower, pr.alpha);
     const float num = Ua - uf * Ua + uf * La;
     f = powf(num / (La * Ua), -1.0f / pr.alpha);
+  } else if (pr.kind == SMCDET_PRIOR_NORMAL) {
+    // Normal(mean, sd) by inverse CDF; u on the generator's 2^-24 grid (u01,
+    // torch.rand: 2u - 1 is then exact), its ends pulled in to 2^-25 and
+    // 1 - 2^-24 so that u = 0 stays finite (smcdet_hip.h, SMCDET_PRIOR_NORMAL)
+    const float uc = fminf(fmaxf(uf, 0x1p-25f), 1.0f - 0x1p-24f);
+    const float z = erfinv_fast(2.0f * uc - 1.0f) * kSqrt2;
+    f = fmaf(nrm_sd(pr), z, nrm_mean(pr));
   } else {
     // Pareto(scale, alpha) by inverse CDF
     f = pr.lower * powf(1.0f - uf, -1.0f / pr.alpha);

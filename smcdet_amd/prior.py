@@ -1,8 +1,8 @@
 """Marked point-process priors (drop-in for smcdet/prior.py).
 
 Kept: `PointProcessPrior` (prior.py:8-75), `PoissonProcessPrior` (:78-101),
-`ParetoStarPrior` (:157-189), `M71Prior` (:192-226) with the reference
-constructors, attributes, `sample()` and `log_prob()`.
+`StarPrior` (:125-154), `ParetoStarPrior` (:157-189), `M71Prior` (:192-226)
+with the reference constructors, attributes, `sample()` and `log_prob()`.
 
 `sample(stratify_by_count=True, ...)` — what SMCsampler.initialize uses — and
 `log_prob` run as gfx950 kernels (smcdet_prior_sample / smcdet_log_prior).
@@ -110,8 +110,8 @@ class PointProcessPrior(object):
     @_hip.cached_struct
     def _cprior(self):
         raise NotImplementedError(
-            f"{type(self).__name__} has no flux prior; the HIP path supports M71Prior and "
-            "ParetoStarPrior")
+            f"{type(self).__name__} has no flux prior; the HIP path supports M71Prior, "
+            "ParetoStarPrior and StarPrior")
 
     def _fill_common(self, c):
         c.min_objects = int(self.min_objects)
@@ -231,6 +231,49 @@ class PoissonProcessPrior(PointProcessPrior):
     def poisson_mean(self):
         return _f32(self.counts_rate * (self.image_height + 2 * self.pad)
                     * (self.image_width + 2 * self.pad))
+
+
+class StarPrior(PointProcessPrior):
+    """prior.py:125-154: Normal(flux_mean, flux_stdev) fluxes.
+
+    On the HIP path with the Poisson `ImageModel` (every use in the reference):
+    the samplers refuse it with `M71ImageModel`, and `MHsampler` and
+    `Aggregate` refuse it.  A Normal flux may be <= 0; a flux
+    of 0 is not replaced in `log_prob` (the reference has no substitution
+    here, unlike :187 and :224)."""
+
+    def __init__(self, *args, flux_mean, flux_stdev, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.flux_mean = flux_mean
+        self.flux_stdev = flux_stdev
+        self.flux_prior = torch.distributions.Normal(self.flux_mean, self.flux_stdev)
+
+    def _sample_flux(self, shape, device):
+        return _f32(self.flux_mean) + _f32(self.flux_stdev) * torch.randn(*shape, device=device)
+
+    @_hip.cached_struct
+    def _cprior(self):
+        c = self._fill_common(_hip.PriorC())
+        c.kind = _hip.SMCDET_PRIOR_NORMAL
+        c.flux_alpha = 0.0
+        c.flux_lower = _f32(self.flux_mean)   # (smcdet_prior_t's field reuse, smcdet_hip.h)
+        c.flux_upper = _f32(self.flux_stdev)
+        return c
+
+
+def refuse_star_prior(prior, image_model=None, where="sampler"):
+    """NotImplementedError at construction where the HIP path has no StarPrior
+    variant: everywhere with `image_model` an M71ImageModel (the Normal family
+    of the sweeps is compiled for the Poisson model), and -- without
+    `image_model` -- in `where` as a whole (MHsampler, Aggregate)."""
+    if not isinstance(prior, StarPrior):
+        return
+    if image_model is None:
+        raise NotImplementedError(f"{where} does not support StarPrior (Normal fluxes)")
+    from .images import M71ImageModel
+    if isinstance(image_model, M71ImageModel):
+        raise NotImplementedError(f"{where}: StarPrior (Normal fluxes) runs with the Poisson "
+                                  "ImageModel only, not M71ImageModel")
 
 
 class ParetoStarPrior(PointProcessPrior):

@@ -48,6 +48,8 @@ class SMCsampler(object):
         # image model run from global memory
         from .images import M71ImageModel
         from .kernel import SingleComponentMALA, SingleComponentMH
+        from .prior import refuse_star_prior
+        refuse_star_prior(Prior, ImageModel, "SMCsampler")
         global_ok = (isinstance(MutationKernel, SingleComponentMH)
                      and not isinstance(MutationKernel, SingleComponentMALA)
                      and isinstance(ImageModel, M71ImageModel))
@@ -747,6 +749,10 @@ class MHsampler(object):
                  flux_detection_threshold, num_samples_total, num_samples_burnin,
                  keep_every_k: int = 1, print_every: int = 1000, *, num_chains=1, seed=None,
                  device=None):
+        from .prior import refuse_star_prior
+        # (the reference's MHsampler reads Prior.flux_lower / flux_upper below,
+        # which StarPrior does not have)
+        refuse_star_prior(Prior, where="MHsampler")
         _hip.check_limits(tile_dim, tile_dim, Prior.max_objects,
                           R=getattr(ImageModel, "psf_radius", None), where="MHsampler")
         if device is None:
