@@ -942,6 +942,77 @@ int smcdet_extract(const float* images, const float* background, const float* si
                    int32_t* counts, float* locs, float* fluxes,
                    int32_t* n_found, int32_t* segmap, void* stream);
 
+/* ---- image-model fit (added under SMCDET_ABI_VERSION 20) ------------------
+ * The objective of the reference's image-model fit (experiments/m71/m71.ipynb,
+ * "Optimize image model parameters"): the masked Gaussian negative
+ * log-likelihood of F calibration fields under the M71 image model with the
+ * catalog held fixed, its gradient and its expected Fisher information in the
+ * logs of the P = SMCDET_FIT_PARAMS parameters, in float64.
+ * Additive: a new entry point; no struct changed. */
+#define SMCDET_FIT_PARAMS 10       /* log_theta, grad; information is [P,P] */
+#define SMCDET_FIT_TERMS 66        /* 1 + P + P(P+1)/2 sums per workgroup */
+#define SMCDET_FIT_BLOCK 16        /* a workgroup owns 16 x 16 pixels */
+#define SMCDET_FIT_NORM_BLOCKS 64  /* workgroups of the normaliser launch */
+#define SMCDET_FIT_NORM_SUMS 7     /* sums each of them leaves */
+#define SMCDET_FIT_MAX_BLOCKS 16777215 /* F * ceil(H/16) * ceil(W/16): one launch's threads < 2^32 */
+/* float64 of workspace smcdet_fit_objective needs: the normaliser's partial
+ * sums, then SMCDET_FIT_TERMS per pixel workgroup */
+#define SMCDET_FIT_WORKSPACE_DOUBLES(F, H, W)                                          \
+  ((int64_t)SMCDET_FIT_NORM_BLOCKS * SMCDET_FIT_NORM_SUMS +                            \
+   (int64_t)SMCDET_FIT_TERMS * (F) * (((H) + SMCDET_FIT_BLOCK - 1) / SMCDET_FIT_BLOCK) * \
+       (((W) + SMCDET_FIT_BLOCK - 1) / SMCDET_FIT_BLOCK))
+
+/* log_theta (host, 10 float64): the logs of
+ *   adu_per_nmgy g, sigma1, sigma2, sigmap, beta, b, p0,
+ *   noise_multiplicative nm, noise_additive na, background B
+ * in this order; the three sigmas are variances (images.py:137-141).
+ * Model, every operation in float64 (the float32 inputs are widened exactly):
+ *   u(r2) = (exp(-r2/(2 sigma1)) + b exp(-r2/(2 sigma2))
+ *            + p0 (1 + r2/(beta sigmap))^(-beta/2)) / (1 + b + p0)
+ *   C     = sum of u over the (32R)^2 grid of pixel-centre offsets
+ *           (i + 1/2 - 16R, j + 1/2 - 16R), i, j = 0 .. 32R-1 (images.py:122-135)
+ *   lambda_p = B + g sum_d f_d u(r2_pd) / C over the stars d < counts[f] whose
+ *           (2R+1)^2 window anchored at floor(loc_d) holds pixel p = (ph, pw),
+ *           r2_pd = (ph + 1/2 - h_d)^2 + (pw + 1/2 - w_d)^2, in catalog order
+ *   v_p   = na + nm lambda_p
+ *   nll   = sum over the pixels with mask != 0 of
+ *           log(2 pi v_p) / 2 + (x_p - lambda_p)^2 / (2 v_p)
+ *   grad[i] = d nll / d log_theta[i]
+ *   information[i,j] = sum over the same pixels of
+ *           lambda_i lambda_j / v + v_i v_j / (2 v^2),
+ *           lambda_i = d lambda / d log_theta[i], v_i likewise (symmetric, both
+ *           triangles written).
+ * images [F,H,W] float32; mask [F,H,W] uint8, null = every pixel; locs [F,D,2]
+ * (row h, column w) and fluxes [F,D] float32; counts [F] int32 (clamped to
+ * 0..D), null = D stars in every field.  The F fields share log_theta and
+ * their sums add.  D = 0 (locs and fluxes may then be null) gives the
+ * background-only result.  R = 0 has an empty normaliser grid (C = 0): the
+ * outputs are finite only without stars.
+ * Outputs, device: nll [1], grad [10], information [10,10] float64; rate
+ * [F,H,W] float32 (nullable): lambda_p of every pixel, masked ones included,
+ * rounded to float32 once.  workspace: SMCDET_FIT_WORKSPACE_DOUBLES(F, H, W)
+ * float64 of caller-owned device memory (workspace_doubles says how many
+ * there are), every word the launches read is written by them first.
+ * Three launches on `stream`, no host round trip between them: the
+ * normaliser's seven sums over one quadrant of its grid (fixed strides, a
+ * fixed tree per workgroup); the pixels (a workgroup per 16 x 16 block, the
+ * field's stars staged through LDS 256 at a time and compacted, in catalog
+ * order, to those whose clipped window meets the block; per workgroup a fixed
+ * tree over its pixels into the workspace); one fixed-order sum over the
+ * workgroups.  No atomics: the same bits on every run.
+ * A null required buffer, F, H or W < 1, D < 0, psf_radius outside 0..64, a
+ * non-finite log_theta or a workspace that is too small: SMCDET_EINVAL.
+ * F*H*W or F*D above 2^31-1, or more than SMCDET_FIT_MAX_BLOCKS pixel blocks
+ * (F * ceil(H/16) * ceil(W/16): many tiny fields): SMCDET_EUNSUPPORTED.
+ * Everything is checked before any device work.  Non-finite locs are not
+ * checked here: such a star's window is taken to miss the field (the Python
+ * wrapper refuses them). */
+int smcdet_fit_objective(const double* log_theta, const float* images, const uint8_t* mask,
+                         const float* locs, const float* fluxes, const int32_t* counts,
+                         int32_t F, int32_t H, int32_t W, int32_t D, int32_t psf_radius,
+                         double* nll, double* grad, double* information, float* rate,
+                         double* workspace, int64_t workspace_doubles, void* stream);
+
 /* ---- tile aggregation (smcdet/aggregate.py:8-593, Aggregate) ------------- */
 #define SMCDET_AGG_MAX_SOURCES 4096
 

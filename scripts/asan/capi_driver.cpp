@@ -394,6 +394,41 @@ int main() {
     EXPECT(CHAIN_STATS(5, 4, 4098, 1, 7, 0, d, d, cneed - 1), SMCDET_EINVAL);
 #undef CHAIN_STATS
   }
+  // image-model fit: nulls, sizes, psf_radius, a non-finite log_theta (a host
+  // array the validation reads), the workspace requirement, the 2^31-1 limits
+  {
+    double* dd = (double*)d;
+    const uint8_t* mk = (const uint8_t*)d;
+    double th[SMCDET_FIT_PARAMS] = {0};
+    const int64_t fneed = SMCDET_FIT_WORKSPACE_DOUBLES(2, 17, 33);
+    EXPECT(fneed == 64 * 7 + 66 * 2 * 2 * 3 ? 0 : 1, 0);
+#define FIT(theta, img, lc, fl, F, H, W, D, R, out, wsp, wsn)                                   \
+  smcdet_fit_objective(theta, img, mk, lc, fl, ws, F, H, W, D, R, out, dd, dd, nullptr, wsp, wsn, \
+                       nullptr)
+    EXPECT(FIT(nullptr, d, d, d, 2, 17, 33, 4, 8, dd, dd, fneed), SMCDET_EINVAL);
+    EXPECT(FIT(th, nullptr, d, d, 2, 17, 33, 4, 8, dd, dd, fneed), SMCDET_EINVAL);
+    EXPECT(FIT(th, d, nullptr, d, 2, 17, 33, 4, 8, dd, dd, fneed), SMCDET_EINVAL);
+    EXPECT(FIT(th, d, d, nullptr, 2, 17, 33, 4, 8, dd, dd, fneed), SMCDET_EINVAL);
+    EXPECT(FIT(th, d, d, d, 2, 17, 33, 4, 8, nullptr, dd, fneed), SMCDET_EINVAL);
+    EXPECT(FIT(th, d, d, d, 2, 17, 33, 4, 8, dd, nullptr, fneed), SMCDET_EINVAL);
+    EXPECT(FIT(th, d, d, d, 2, 17, 33, 4, 8, dd, dd, fneed - 1), SMCDET_EINVAL);
+    EXPECT(FIT(th, d, d, d, 0, 17, 33, 4, 8, dd, dd, fneed), SMCDET_EINVAL);
+    EXPECT(FIT(th, d, d, d, 2, 0, 33, 4, 8, dd, dd, fneed), SMCDET_EINVAL);
+    EXPECT(FIT(th, d, d, d, 2, 17, -3, 4, 8, dd, dd, fneed), SMCDET_EINVAL);
+    EXPECT(FIT(th, d, d, d, 2, 17, 33, -1, 8, dd, dd, fneed), SMCDET_EINVAL);
+    EXPECT(FIT(th, d, d, d, 2, 17, 33, 4, -1, dd, dd, fneed), SMCDET_EINVAL);
+    EXPECT(FIT(th, d, d, d, 2, 17, 33, 4, 65, dd, dd, fneed), SMCDET_EINVAL);
+    EXPECT(FIT(th, d, d, d, 3, 32768, 32768, 4, 8, dd, dd, fneed), SMCDET_EUNSUPPORTED);
+    EXPECT(FIT(th, d, d, d, 32768, 17, 33, 65536, 8, dd, dd, fneed), SMCDET_EUNSUPPORTED);
+    // many tiny fields: more 16x16 blocks than one launch takes
+    EXPECT(FIT(th, d, d, d, 1 << 24, 1, 1, 4, 8, dd, dd, fneed), SMCDET_EUNSUPPORTED);
+    EXPECT(FIT(th, d, d, d, SMCDET_FIT_MAX_BLOCKS, 1, 1, 4, 8, dd, dd, fneed), SMCDET_EINVAL);
+    th[SMCDET_FIT_PARAMS - 1] = __builtin_nan("");
+    EXPECT(FIT(th, d, d, d, 2, 17, 33, 4, 8, dd, dd, fneed), SMCDET_EINVAL);
+    th[SMCDET_FIT_PARAMS - 1] = -__builtin_inf();
+    EXPECT(FIT(th, d, d, d, 2, 17, 33, 4, 8, dd, dd, fneed), SMCDET_EINVAL);
+#undef FIT
+  }
   EXPECT(smcdet_count_posterior(d, d, 0, 1, 100000, 4, 1, 4, SMCDET_RESAMPLE_SYSTEMATIC, 0, 0,
                                 nullptr, nullptr, d, d, d, d, idx, d, d, d, nullptr),
          SMCDET_EUNSUPPORTED);

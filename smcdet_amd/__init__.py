@@ -12,7 +12,9 @@ posteriors, interval coverage, quantile bands and bootstrap bands;
 `convergence` (not in the reference) gives split-R-hat, effective sample sizes
 and Monte Carlo standard errors of MCMC chains; `extract` (the scripts'
 run_sep.py baseline, without sep) is a classical multi-threshold source
-extractor with the grid search of its hyperparameters for F1.
+extractor with the grid search of its hyperparameters for F1; `fit` (the
+reference's m71.ipynb, "Optimize image model parameters") fits the M71 image
+model's parameters to calibration fields with a fixed catalog.
 """
 import importlib
 import sys
@@ -22,7 +24,8 @@ from . import _hip  # noqa: F401
 __version__ = "0.1.0"
 
 _DROP_IN = ("sampler", "kernel", "images", "prior", "distributions", "aggregate",
-            "metrics", "condense", "predictive", "calibration", "convergence", "extract")
+            "metrics", "condense", "predictive", "calibration", "convergence", "extract",
+            "fit")
 
 
 def install_as_smcdet():

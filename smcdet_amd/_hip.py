@@ -65,6 +65,12 @@ CHAINS_MAX_RHO = 1024       # SMCDET_CHAINS_MAX_RHO: autocorrelations returned p
 CHAINS_LDS_DRAWS = 16384    # SMCDET_CHAINS_LDS_DRAWS: rows up to this keep their draws in LDS
 CHAINS_BLOCK_PAIRS = 8      # SMCDET_CHAINS_BLOCK_PAIRS: lag pairs per test of the stopping rule
 EXTRACT_MAX_PIXELS = 1024   # SMCDET_EXTRACT_MAX_PIXELS: H*W of an image of smcdet_extract
+FIT_PARAMS = 10             # SMCDET_FIT_PARAMS: log-parameters of smcdet_fit_objective
+FIT_TERMS = 66              # SMCDET_FIT_TERMS: sums per pixel workgroup (nll, grad, upper triangle)
+FIT_BLOCK = 16              # SMCDET_FIT_BLOCK: a pixel workgroup owns 16 x 16 pixels
+FIT_NORM_BLOCKS = 64        # SMCDET_FIT_NORM_BLOCKS: workgroups of the normaliser launch
+FIT_NORM_SUMS = 7           # SMCDET_FIT_NORM_SUMS: sums each of them leaves
+FIT_MAX_BLOCKS = 16777215   # SMCDET_FIT_MAX_BLOCKS: F * ceil(H/16) * ceil(W/16) of one call
 
 
 def check_limits(H, W, S, N=None, T=None, R=None, where="sampler", global_ok=False):
@@ -195,6 +201,8 @@ _SIGS = {
     "smcdet_chain_stats_workspace": ([c_i, c_i, c_i, c_i], c_i64),
     "smcdet_extract": ([c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p,
                         c_p, c_p, c_p, c_p], c_i),
+    "smcdet_fit_objective": ([c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p,
+                              c_p, c_p, c_i64, c_p], c_i),
     "smcdet_aggregate_sweep": ([c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p,
                                 c_p, c_p, c_p, c_u64, c_u64, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                 c_p], c_i),
@@ -246,6 +254,7 @@ _OUTS = {
     "smcdet_chain_stats": (tuple(range(7, 20)), ()),
     "smcdet_chain_stats_workspace": ((), ()),
     "smcdet_extract": ((13, 14, 15, 16, 17), ()),
+    "smcdet_fit_objective": ((11, 12, 13, 14, 15), ()),
     "smcdet_aggregate_sweep": ((13, 14, 15, 19, 20, 21, 22, 24), ((10, 13), (11, 14), (12, 15))),
     "smcdet_aggregate_temper": ((10,), ()),
     "smcdet_aggregate_reweight": ((10, 11, 12, 13, 17), ()),
@@ -346,7 +355,7 @@ SOURCES = tuple(os.path.join(_REPO, p) for p in (
     "smcdet_amd/csrc/agg_kernel.hip", "smcdet_amd/csrc/match_kernel.hip",
     "smcdet_amd/csrc/condense_kernel.hip", "smcdet_amd/csrc/predictive_kernel.hip",
     "smcdet_amd/csrc/summary_kernel.hip", "smcdet_amd/csrc/convergence_kernel.hip",
-    "smcdet_amd/csrc/extract_kernel.hip",
+    "smcdet_amd/csrc/extract_kernel.hip", "smcdet_amd/csrc/fit_kernel.hip",
     "smcdet_amd/csrc/device.h", "smcdet_amd/csrc/render.h",
     "smcdet_amd/csrc/mcmc.h", "smcdet_amd/csrc/tile.h", "smcdet_amd/csrc/mh_plan.h",
     "include/smcdet_hip.h"))
