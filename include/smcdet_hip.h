@@ -1013,6 +1013,87 @@ int smcdet_fit_objective(const double* log_theta, const float* images, const uin
                          double* nll, double* grad, double* information, float* rate,
                          double* workspace, int64_t workspace_doubles, void* stream);
 
+/* ---- forced PSF photometry (added under SMCDET_ABI_VERSION 20) ------------
+ * Positions are held fixed and the image model is given; the fluxes of all
+ * sources of a problem are solved jointly (they blend) by iteratively
+ * reweighted least squares, each with its Cramér–Rao error: the crowded-field
+ * baseline (DAOPHOT-style flux fitting) next to smcdet_extract, and a
+ * per-detection check of condensed posterior catalogs.  Positions are never
+ * fitted.  The definition below is this project's own; the reference has no
+ * such code.  Additive: a new entry point; no struct changed. */
+#define SMCDET_PHOT_MAX_SOURCES 32    /* K: position slots of a problem */
+#define SMCDET_PHOT_MAX_ITER 16       /* n_iter */
+#define SMCDET_PHOT_FIT_BACKGROUND 1u /* flags: the background is a free parameter */
+/* status bits */
+#define SMCDET_PHOT_DROPPED 1    /* a source's column is all zero: flux and error NaN */
+#define SMCDET_PHOT_SINGULAR 2   /* a squared pivot below 1e-8: the whole problem NaN */
+#define SMCDET_PHOT_BACKGROUND 4 /* background[t] is not positive and finite: as singular */
+
+/* One problem is image t = images[t] (model->H x model->W pixels) with
+ * position list g: counts [T,G] int32 (clamped to 0..K) and locs [T,G,K,2]
+ * float32 (row h, column w), T*G problems, g fastest; the G lists of an image
+ * share it (the layout of smcdet_extract's outputs and of a population
+ * [T,N,S,2]).  background [T] float32, nullable: per-image B, else
+ * model->background; B must be > 0 and finite.  g = adu_per_nmgy (1 for
+ * SMCDET_MODEL_POISSON).  Variance v = na + nm * lambda with na =
+ * noise_additive, nm = noise_multiplicative; SMCDET_MODEL_POISSON is taken as
+ * Gaussian with v = lambda (na = 0, nm = 1), an approximation of its Poisson
+ * likelihood that is good where the rates are large.
+ * 1. Columns: phi_pk, the normalised PSF of source k at pixel p = (ph, pw), is
+ *    non-zero only inside the (2R+1)^2 window anchored at floor(loc_k),
+ *    clipped to the image; it is evaluated in float32 exactly as the render
+ *    evaluates it (dh = (ph + 0.5f) - h, dw alike, r2 = fma(dh, dh, dw*dw), the
+ *    profile's three hardware exponentials) and then widened.  Everything
+ *    after this point is float64.
+ * 2. Skipped: a slot at or past counts[t,g], and a slot whose location is not
+ *    finite: flux 0, error NaN, no parameter.  Dropped: a source whose column
+ *    is all zero (its window misses the image): no parameter, flux and error
+ *    NaN, status bit SMCDET_PHOT_DROPPED.  The other sources, in slot order,
+ *    and then the background with SMCDET_PHOT_FIT_BACKGROUND, are the P free
+ *    parameters theta.
+ * 3. Initial variance v_p = na + nm * max(x_p, B/4).  The floor B/4 applies to
+ *    lambda_p in every later variance: a guard against non-positive
+ *    variances, not a model.
+ * 4. n_iter (1..SMCDET_PHOT_MAX_ITER) times: A = D^T W D, b = D^T W y with W =
+ *    diag(1/v); columns D_k = g phi_k; without SMCDET_PHOT_FIT_BACKGROUND y =
+ *    x - B, with it D gains a column of ones and y = x.  A is scaled to a unit
+ *    diagonal (A_ij / sqrt(A_ii A_jj), b_i / sqrt(A_ii)), Cholesky-factored
+ *    and solved; lambda = D theta (+ B), v = na + nm * max(lambda, B/4).  A
+ *    squared pivot of the scaled factor below 1e-8 (or not a number) makes
+ *    the problem singular: status bit SMCDET_PHOT_SINGULAR, and every flux and
+ *    error of its free and dropped sources, its background_out and its chi2
+ *    are NaN.  (Two identical positions, or positions 1e-4 px apart, are
+ *    singular; a pair 0.3 px apart has pivots near 1e-2.)  Fluxes are not
+ *    constrained to be non-negative.
+ * 5. Outputs at the final theta and v, float64: fluxes [T,G,K] (nmgy);
+ *    flux_err [T,G,K] = sqrt(diag(I^-1)), I_ij = sum_p D_pi D_pj / v_p +
+ *    (nm D_pi)(nm D_pj) / (2 v_p^2), the expected Fisher information over the
+ *    free parameters, inverted through the Cholesky factor of its
+ *    unit-diagonal scaling (the same pivot rule); background_out [T,G], fitted
+ *    or given; chi2 [T,G] = sum_p (x_p - lambda_p)^2 / v_p; n_pixels [T,G] int32
+ *    = H*W; n_free [T,G] int32 = P; status [T,G] int32; cov [T,G,K,K]
+ *    (nullable): the sources' block of I^-1, symmetric bit for bit, NaN in
+ *    the rows and columns of slots that are not free.
+ * One wavefront per problem, pixel p on lane p % 64; the normal matrix, its
+ * factor and the factor's inverse are packed lower-triangular float64 in the
+ * wave's LDS slab (2 x 561 for K = 32 and the background).  Every sum runs in
+ * a fixed order (per lane ascending p, then one float64 wave reduction per
+ * matrix entry); no atomics: the same bits on every run, in every launch and
+ * behind every allocation.
+ * H*W > SMCDET_EXTRACT_MAX_PIXELS, K > SMCDET_PHOT_MAX_SOURCES, psf_radius
+ * outside 0..64, T*G above 2^31-1: SMCDET_EUNSUPPORTED; a null required
+ * buffer, a size below 1, n_iter outside its range, unknown flags, a model
+ * background that is not positive and finite when background is null, noise
+ * parameters that do not give a positive variance: SMCDET_EINVAL.  Everything
+ * is checked before any device work; a per-image background that is not
+ * positive and finite is found on the device (SMCDET_PHOT_BACKGROUND). */
+int smcdet_forced_photometry(const smcdet_image_model_t* model, const float* images,
+                             const int32_t* counts, const float* locs, const float* background,
+                             int32_t T, int32_t G, int32_t K, int32_t n_iter, uint32_t flags,
+                             double* fluxes, double* flux_err, double* background_out,
+                             double* chi2, int32_t* n_pixels, int32_t* n_free, int32_t* status,
+                             double* cov, void* stream);
+
 /* ---- tile aggregation (smcdet/aggregate.py:8-593, Aggregate) ------------- */
 #define SMCDET_AGG_MAX_SOURCES 4096
 

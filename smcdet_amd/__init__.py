@@ -14,7 +14,10 @@ and Monte Carlo standard errors of MCMC chains; `extract` (the scripts'
 run_sep.py baseline, without sep) is a classical multi-threshold source
 extractor with the grid search of its hyperparameters for F1; `fit` (the
 reference's m71.ipynb, "Optimize image model parameters") fits the M71 image
-model's parameters to calibration fields with a fixed catalog.
+model's parameters to calibration fields with a fixed catalog; `photometry`
+(not in the reference) is forced PSF photometry: the joint flux solve at fixed
+positions with Cramér–Rao errors, for `extract`'s detections and for condensed
+posterior detections.
 """
 import importlib
 import sys
@@ -25,7 +28,7 @@ __version__ = "0.1.0"
 
 _DROP_IN = ("sampler", "kernel", "images", "prior", "distributions", "aggregate",
             "metrics", "condense", "predictive", "calibration", "convergence", "extract",
-            "fit")
+            "fit", "photometry")
 
 
 def install_as_smcdet():

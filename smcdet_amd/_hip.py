@@ -71,6 +71,12 @@ FIT_BLOCK = 16              # SMCDET_FIT_BLOCK: a pixel workgroup owns 16 x 16 p
 FIT_NORM_BLOCKS = 64        # SMCDET_FIT_NORM_BLOCKS: workgroups of the normaliser launch
 FIT_NORM_SUMS = 7           # SMCDET_FIT_NORM_SUMS: sums each of them leaves
 FIT_MAX_BLOCKS = 16777215   # SMCDET_FIT_MAX_BLOCKS: F * ceil(H/16) * ceil(W/16) of one call
+PHOT_MAX_SOURCES = 32       # SMCDET_PHOT_MAX_SOURCES: position slots of a photometry problem
+PHOT_MAX_ITER = 16          # SMCDET_PHOT_MAX_ITER: reweighting iterations
+PHOT_FIT_BACKGROUND = 1     # SMCDET_PHOT_FIT_BACKGROUND
+PHOT_DROPPED = 1            # SMCDET_PHOT_DROPPED (status bit): a source's column is all zero
+PHOT_SINGULAR = 2           # SMCDET_PHOT_SINGULAR (status bit)
+PHOT_BACKGROUND = 4         # SMCDET_PHOT_BACKGROUND (status bit)
 
 
 def check_limits(H, W, S, N=None, T=None, R=None, where="sampler", global_ok=False):
@@ -203,6 +209,8 @@ _SIGS = {
                         c_p, c_p, c_p, c_p], c_i),
     "smcdet_fit_objective": ([c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p,
                               c_p, c_p, c_i64, c_p], c_i),
+    "smcdet_forced_photometry": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_u32, c_p, c_p, c_p,
+                                  c_p, c_p, c_p, c_p, c_p, c_p], c_i),
     "smcdet_aggregate_sweep": ([c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p,
                                 c_p, c_p, c_p, c_u64, c_u64, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                 c_p], c_i),
@@ -255,6 +263,7 @@ _OUTS = {
     "smcdet_chain_stats_workspace": ((), ()),
     "smcdet_extract": ((13, 14, 15, 16, 17), ()),
     "smcdet_fit_objective": ((11, 12, 13, 14, 15), ()),
+    "smcdet_forced_photometry": (tuple(range(10, 18)), ()),
     "smcdet_aggregate_sweep": ((13, 14, 15, 19, 20, 21, 22, 24), ((10, 13), (11, 14), (12, 15))),
     "smcdet_aggregate_temper": ((10,), ()),
     "smcdet_aggregate_reweight": ((10, 11, 12, 13, 17), ()),
@@ -356,6 +365,7 @@ SOURCES = tuple(os.path.join(_REPO, p) for p in (
     "smcdet_amd/csrc/condense_kernel.hip", "smcdet_amd/csrc/predictive_kernel.hip",
     "smcdet_amd/csrc/summary_kernel.hip", "smcdet_amd/csrc/convergence_kernel.hip",
     "smcdet_amd/csrc/extract_kernel.hip", "smcdet_amd/csrc/fit_kernel.hip",
+    "smcdet_amd/csrc/photometry_kernel.hip",
     "smcdet_amd/csrc/device.h", "smcdet_amd/csrc/render.h",
     "smcdet_amd/csrc/mcmc.h", "smcdet_amd/csrc/tile.h", "smcdet_amd/csrc/mh_plan.h",
     "include/smcdet_hip.h"))

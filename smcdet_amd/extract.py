@@ -64,7 +64,7 @@ class Tuning(NamedTuple):
     settings: torch.Tensor  # [G,4] float64 (cpu)
 
 
-def _image_shape(images):
+def _image_shape(images, where="extract"):
     """Type and shape of `images` (checked before anything needs a device)."""
     if not isinstance(images, torch.Tensor):
         raise TypeError("images must be a torch.Tensor")
@@ -74,7 +74,7 @@ def _image_shape(images):
         raise ValueError(f"images must be [T,H,W] or [H,W], got {tuple(images.shape)}")
     H, W = images.shape[1:]
     if H < 1 or W < 1 or H * W > _hip.EXTRACT_MAX_PIXELS:
-        raise ValueError(f"extract: a {H}x{W} image has {H * W} pixels, outside "
+        raise ValueError(f"{where}: a {H}x{W} image has {H * W} pixels, outside "
                          f"1..{_hip.EXTRACT_MAX_PIXELS} (a problem lives in one wavefront's LDS "
                          "slab)")
     return images
@@ -217,15 +217,33 @@ def extract(images, background, sigma, thresh, minarea=5, deblend_nthresh=32, de
 def tune(images, background, sigma, true_counts, true_locs, true_fluxes, thresh, minarea=(5,),
          deblend_cont=(0.005,), clean_param=(1.0,), deblend_nthresh=32, clean=True,
          max_detections=16, locs_tol=0.5, mags_tol=0.5, mag_bins=(14.0,), flux_scale=1.0,
-         max_bytes=1 << 30):
+         max_bytes=1 << 30, flux="isophotal", image_model=None):
     """The scripts' grid search: extract_grid on held-out images, one
     match_catalogs(..., None, ...) against the truth (true_counts [T],
     true_locs [T,St,2], true_fluxes [T,St]), and per setting the F1 of the last
     magnitude bin pooled over the images.  Returns Tuning(f1 [G], best, ...):
     best is the first maximum in grid order.  Everything runs on the device;
-    the grid is cut into chunks of settings whose outputs stay below max_bytes."""
+    the grid is cut into chunks of settings whose outputs stay below max_bytes.
+    flux="psf": the detections are scored with their forced PSF fluxes under
+    image_model (photometry.photometry_of: one more launch per chunk between
+    extract and match; nmgy, so flux_scale applies only to the isophotal flux
+    a failed solve falls back to; max_detections <= 32)."""
     if int(max_bytes) < 1:
         raise ValueError("max_bytes must be positive")
+    if flux not in ("isophotal", "psf"):
+        raise ValueError(f"flux = {flux!r} must be 'isophotal' or 'psf'")
+    if flux == "psf" and image_model is None:
+        raise ValueError("flux='psf' needs image_model")
+    if flux == "isophotal" and image_model is not None:
+        raise ValueError("image_model is used only with flux='psf'")
+    if flux == "psf":
+        from . import photometry
+        photometry._check_model(image_model, *_image_shape(images).shape[1:])
+        if isinstance(max_detections, int) and max_detections > _hip.PHOT_MAX_SOURCES:
+            raise ValueError(f"flux='psf': max_detections = {max_detections} above "
+                             f"{_hip.PHOT_MAX_SOURCES}")
+        if not float(image_model.background) > 0:
+            raise ValueError("the image model's background must be positive")
     images, background, sigma, settings, flux_scale = _prepare(
         images, background, sigma, thresh, minarea, deblend_cont, clean, clean_param,
         deblend_nthresh, max_detections, flux_scale)
@@ -235,6 +253,10 @@ def tune(images, background, sigma, true_counts, true_locs, true_fluxes, thresh,
     bins = torch.as_tensor(mag_bins, dtype=torch.float32).reshape(-1)
     # counts, n_found, locs, fluxes of extract and the four float32 [.,B] tables of the matching
     per_setting = T * (8 + 12 * K + 16 * bins.numel())
+    if flux == "psf":
+        cm = image_model._cmodel()
+        # fluxes and errors (float64), background, chi2, three int32, the replaced fluxes
+        per_setting += T * (16 * K + 16 + 12 + 4 * K)
     chunk = max(1, min(G, int(max_bytes) // per_setting))
     f1 = torch.empty(G, device=images.device, dtype=torch.float32)
     for g0 in range(0, G, chunk):
@@ -242,6 +264,9 @@ def tune(images, background, sigma, true_counts, true_locs, true_fluxes, thresh,
                                              deblend_nthresh, K, False)
         if flux_scale != 1.0:
             fluxes = fluxes / flux_scale
+        if flux == "psf":
+            phot = photometry._launch(images, counts, locs, cm, None, 4, False, False)
+            fluxes = photometry._psf_fluxes(phot.fluxes, fluxes)
         tt, tm, et, em = match_catalogs(true_counts, true_locs, true_fluxes, counts, locs, fluxes,
                                         None, locs_tol, mags_tol, bins)
         # compute_precision_recall_f1 per setting: pooled over the images, last bin
