@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result
 CSRC := smcdet_amd/csrc
-SRCS := $(CSRC)/common.hip $(CSRC)/model_kernels.hip $(CSRC)/mh_kernel.hip $(CSRC)/mala_kernel.hip $(CSRC)/chain_kernel.hip $(CSRC)/smc_kernels.hip $(CSRC)/agg_kernel.hip $(CSRC)/match_kernel.hip $(CSRC)/condense_kernel.hip $(CSRC)/predictive_kernel.hip $(CSRC)/summary_kernel.hip $(CSRC)/convergence_kernel.hip $(CSRC)/extract_kernel.hip $(CSRC)/fit_kernel.hip $(CSRC)/photometry_kernel.hip
+SRCS := $(CSRC)/common.hip $(CSRC)/model_kernels.hip $(CSRC)/mh_kernel.hip $(CSRC)/mala_kernel.hip $(CSRC)/chain_kernel.hip $(CSRC)/smc_kernels.hip $(CSRC)/agg_kernel.hip $(CSRC)/match_kernel.hip $(CSRC)/condense_kernel.hip $(CSRC)/predictive_kernel.hip $(CSRC)/summary_kernel.hip $(CSRC)/convergence_kernel.hip $(CSRC)/extract_kernel.hip $(CSRC)/fit_kernel.hip $(CSRC)/photometry_kernel.hip $(CSRC)/find_kernel.hip
 HDRS := $(CSRC)/device.h $(CSRC)/render.h $(CSRC)/mcmc.h $(CSRC)/tile.h $(CSRC)/mh_plan.h include/smcdet_hip.h
 OBJS := $(SRCS:.hip=.o)
 LIB := smcdet_amd/libsmcdet_hip.so

@@ -1094,6 +1094,110 @@ int smcdet_forced_photometry(const smcdet_image_model_t* model, const float* ima
                              double* chi2, int32_t* n_pixels, int32_t* n_free, int32_t* status,
                              double* cov, void* stream);
 
+/* ---- PSF-fitting detector (added under SMCDET_ABI_VERSION 20) -------------
+ * The finder and the position step of DAOPHOT's loop next to
+ * smcdet_forced_photometry: the significance map of an image's residual with
+ * the PSF as matched filter, its peaks, and leave-one-out recentring of listed
+ * sources.  The definition below is this project's own; the reference has no
+ * such code.  Additive: two new entry points; no struct
+ * changed.
+ *
+ * - A problem is one image x[H,W] with one list of n ≤ K sources (`counts
+ *   [T,G]`, `locs [T,G,K,2]`, `fluxes [T,G,K]` float32 nmgy).  The G lists share
+ *   the image.  This is the layout of `extract_grid` and `forced_photometry`.
+ *   A null list means n = 0.
+ * - B is the model's background or a per-image `background [T]` > 0.  g is
+ *   `adu_per_nmgy`.
+ * - The Poisson `ImageModel` is taken as Gaussian with na = 0, nm = 1, g = 1,
+ *   as `photometry` does.
+ * - φ_pk is the render's own float32 profile: `psf_raw`·`psf_scale` of
+ *   `device.h`, the argument formed as in `render.h`.  It is non-zero only in
+ *   the (2R+1)² window anchored at floor(loc), clipped to the image.  It is
+ *   widened to float64 before use.  Everything after is float64 with fixed
+ *   summation order.
+ * - Variance from the data: v_p = na + nm·max(x_p, B/4).  This is the first
+ *   iteration of `smcdet_forced_photometry`, independent of the list.
+ * - A listed source counts if its slot is below the count and its location and
+ *   flux are finite.  Other slots are ignored: not subtracted, never moved,
+ *   never excluding.
+ * - Residual: r_p = x_p − B − g·Σ_k f_k φ_pk over the counted sources.
+ * - For a candidate position c: a_c = Σ_p φ_pc r_p / v_p and d_c = Σ_p
+ *   φ_pc² / v_p over its clipped window.
+ *   - f̂_c = a_c / (g·d_c) is the ML flux of one more source at c with
+ *     everything else held.
+ *   - snr_c = a_c / √d_c, rounded once to float32.
+ *   - A candidate inside the image always has d_c > 0.  A candidate with d_c =
+ *     0 has snr −inf.
+ * A candidate's position is a float32 (the float64 value below rounded once)
+ * when its profile is formed.  counts are clamped to 0..K.  A per-image
+ * background that is not positive and finite gives 1/v = NaN: a map of NaN, no
+ * peak, no move. */
+#define SMCDET_FIND_MAX_CELLS_PER_PIXEL 4 /* cells */
+#define SMCDET_FIND_MAX_CELLS 16384       /* (cells H) (cells W) */
+#define SMCDET_FIND_MAX_NMS 16            /* nms_radius, cells (clamped on the device) */
+#define SMCDET_FIND_MAX_HALF 3            /* half: (2 half + 1)^2 candidates of a move */
+
+/* Map and peaks.  Candidates: `cells` = c in 1..4 per pixel; the grid is cH x
+ * cW = cH·cW cells and cell (i, j) sits at ((i+½)/c, (j+½)/c).  thresh [G]
+ * float32 and nms_radius [G] int32 (0..16) are per setting g; min_sep >= 0 px.
+ * A cell is a peak iff (1) snr >= thresh, compared in float32; (2) it beats
+ * every other cell within Chebyshev distance nms_radius by the total order of
+ * smcdet_map_peaks (a larger value wins, on equality the lower flat index i·cW
+ * + j); (3) its centre lies more than min_sep (Chebyshev, pixels, float64)
+ * from every counted source.  Refinement, per axis, with s-, s0, s+ the
+ * float32 map values: if both neighbours exist and s- − 2 s0 + s+ < 0 then δ =
+ * clamp(½ (s- − s+) / (s- − 2 s0 + s+), ±½), formed in float64, else δ = 0; loc
+ * = centre + δ/c (evaluated as ((i+½) + δ)/c), rounded once to float32.  Peaks
+ * are ordered by descending snr, then ascending flat index; n_found [T,G]
+ * counts all of them and the first K − n are appended.
+ * Outputs: counts_out [T,G]; locs_out [T,G,K,2]: the n given slots copied bit
+ * for bit, the new ones after, NaN past the count; snr_out and flux_hat
+ * [T,G,K] float32 (snr and f̂ at the peak's cell centre): NaN in given and
+ * empty slots; map_out [T,G,cH,cW] float32, nullable.  No output may alias an
+ * input.
+ * One workgroup of 256 threads per problem: r and 1/v per pixel (float64), the
+ * float32 map and the peak bits in LDS (16 H W + 4 cH cW + cH cW / 8 + 544
+ * bytes: 82.5 KiB at both limits); one thread per cell forms a and d over the
+ * cell's clipped window in ascending pixel order by float64 fma, the profile
+ * evaluated in place; peak bits are wave ballots and the K − n selections are
+ * workgroup arg-maxes.  No atomics; the same bits on every run, whatever the
+ * neighbours in the launch.
+ * H·W > SMCDET_EXTRACT_MAX_PIXELS, cH·cW > SMCDET_FIND_MAX_CELLS, K >
+ * SMCDET_PHOT_MAX_SOURCES, psf_radius outside 0..64, T·G above 2^31-1:
+ * SMCDET_EUNSUPPORTED; null required buffers (counts, locs and fluxes are
+ * given together or all null), sizes < 1, cells outside 1..4, a min_sep that
+ * is negative or not finite, a model background that is not positive and
+ * finite when background is null, noise parameters that do not give a
+ * positive variance: SMCDET_EINVAL.  Everything is checked before any device
+ * work. */
+int smcdet_psf_find(const smcdet_image_model_t* model, const float* images,
+                    const float* background, const int32_t* counts, const float* locs,
+                    const float* fluxes, int32_t T, int32_t G, int32_t K, int32_t cells,
+                    const float* thresh, const int32_t* nms_radius, double min_sep,
+                    int32_t* counts_out, float* locs_out, float* snr_out, float* flux_hat,
+                    int32_t* n_found, float* map_out, void* stream);
+
+/* One Jacobi sweep of position moves.  For every counted source k,
+ * independently and from the launch's inputs only: r(k) = r + g·f_k phi_k(old
+ * position); candidates old position + (a, b)·step with a, b in −half..half
+ * (half in 1..3, step > 0; up to 49, row-major, index (a + half)(2 half + 1) +
+ * b + half); snr at each from r(k) and v; the arg-max, the lowest candidate
+ * index on ties; the same per-axis parabola on the candidate grid, in units of
+ * step; new loc = old + (offset + δ)·step, rounded once.
+ * Outputs: locs_out [T,G,K,2] and snr_out [T,G,K], the leave-one-out
+ * significance at the chosen candidate.  Slots that do not count are copied
+ * unchanged (bit for bit), with snr NaN.
+ * One wavefront per problem: the residual's pixel p on lane p % 64, then one
+ * (source, candidate) pair per lane, then source k's arg-max and parabola on
+ * the lane of its slot; LDS 16 H W + 384 + 4 K (2 half + 1)^2 bytes.  No
+ * atomics; the same bits on every run.
+ * Limits and errors as smcdet_psf_find; half outside 1..3, a step that is not
+ * positive and finite, a null buffer: SMCDET_EINVAL. */
+int smcdet_psf_recentre(const smcdet_image_model_t* model, const float* images,
+                        const float* background, const int32_t* counts, const float* locs,
+                        const float* fluxes, int32_t T, int32_t G, int32_t K, int32_t half,
+                        double step, float* locs_out, float* snr_out, void* stream);
+
 /* ---- tile aggregation (smcdet/aggregate.py:8-593, Aggregate) ------------- */
 #define SMCDET_AGG_MAX_SOURCES 4096
 

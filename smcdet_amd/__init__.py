@@ -17,7 +17,9 @@ reference's m71.ipynb, "Optimize image model parameters") fits the M71 image
 model's parameters to calibration fields with a fixed catalog; `photometry`
 (not in the reference) is forced PSF photometry: the joint flux solve at fixed
 positions with Cramér–Rao errors, for `extract`'s detections and for condensed
-posterior detections.
+posterior detections; `psffind` (not in the reference) is the PSF-fitting
+detector around it: the matched-filter significance map of the residual, its
+peaks, leave-one-out recentring, and the grid search of its settings for F1.
 """
 import importlib
 import sys
@@ -28,7 +30,7 @@ __version__ = "0.1.0"
 
 _DROP_IN = ("sampler", "kernel", "images", "prior", "distributions", "aggregate",
             "metrics", "condense", "predictive", "calibration", "convergence", "extract",
-            "fit", "photometry")
+            "fit", "photometry", "psffind")
 
 
 def install_as_smcdet():

@@ -77,6 +77,10 @@ PHOT_FIT_BACKGROUND = 1     # SMCDET_PHOT_FIT_BACKGROUND
 PHOT_DROPPED = 1            # SMCDET_PHOT_DROPPED (status bit): a source's column is all zero
 PHOT_SINGULAR = 2           # SMCDET_PHOT_SINGULAR (status bit)
 PHOT_BACKGROUND = 4         # SMCDET_PHOT_BACKGROUND (status bit)
+FIND_MAX_CELLS_PER_PIXEL = 4  # SMCDET_FIND_MAX_CELLS_PER_PIXEL: cells of smcdet_psf_find
+FIND_MAX_CELLS = 16384      # SMCDET_FIND_MAX_CELLS: cells of a significance map
+FIND_MAX_NMS = 16           # SMCDET_FIND_MAX_NMS: nms_radius, cells
+FIND_MAX_HALF = 3           # SMCDET_FIND_MAX_HALF: (2 half + 1)^2 candidates of a move
 
 
 def check_limits(H, W, S, N=None, T=None, R=None, where="sampler", global_ok=False):
@@ -211,6 +215,10 @@ _SIGS = {
                               c_p, c_p, c_i64, c_p], c_i),
     "smcdet_forced_photometry": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_u32, c_p, c_p, c_p,
                                   c_p, c_p, c_p, c_p, c_p, c_p], c_i),
+    "smcdet_psf_find": ([c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_d, c_p, c_p,
+                         c_p, c_p, c_p, c_p, c_p], c_i),
+    "smcdet_psf_recentre": ([c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_d, c_p, c_p, c_p],
+                            c_i),
     "smcdet_aggregate_sweep": ([c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p,
                                 c_p, c_p, c_p, c_u64, c_u64, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                 c_p], c_i),
@@ -264,6 +272,8 @@ _OUTS = {
     "smcdet_extract": ((13, 14, 15, 16, 17), ()),
     "smcdet_fit_objective": ((11, 12, 13, 14, 15), ()),
     "smcdet_forced_photometry": (tuple(range(10, 18)), ()),
+    "smcdet_psf_find": (tuple(range(13, 19)), ()),
+    "smcdet_psf_recentre": ((11, 12), ()),
     "smcdet_aggregate_sweep": ((13, 14, 15, 19, 20, 21, 22, 24), ((10, 13), (11, 14), (12, 15))),
     "smcdet_aggregate_temper": ((10,), ()),
     "smcdet_aggregate_reweight": ((10, 11, 12, 13, 17), ()),
@@ -365,7 +375,7 @@ SOURCES = tuple(os.path.join(_REPO, p) for p in (
     "smcdet_amd/csrc/condense_kernel.hip", "smcdet_amd/csrc/predictive_kernel.hip",
     "smcdet_amd/csrc/summary_kernel.hip", "smcdet_amd/csrc/convergence_kernel.hip",
     "smcdet_amd/csrc/extract_kernel.hip", "smcdet_amd/csrc/fit_kernel.hip",
-    "smcdet_amd/csrc/photometry_kernel.hip",
+    "smcdet_amd/csrc/photometry_kernel.hip", "smcdet_amd/csrc/find_kernel.hip",
     "smcdet_amd/csrc/device.h", "smcdet_amd/csrc/render.h",
     "smcdet_amd/csrc/mcmc.h", "smcdet_amd/csrc/tile.h", "smcdet_amd/csrc/mh_plan.h",
     "include/smcdet_hip.h"))
